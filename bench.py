@@ -11,12 +11,16 @@ max over ranks between barriers.  ``--mode nll`` benches the config-3 NLL step
 instead (fused inverse + logpdf + fp64 Σ, then an RCCL all-reduce of
 {Σ logpdf, count}).
 
-Rank 0 prints ONE JSON line (bench contract).  Extra objects:
+Rank 0 prints ONE JSON line (bench contract).  A plain run sets up, warms up,
+times the K steps, writes the outputs of the last timed step (``--dump-outputs
+DIR``) and prints the line.  ``--full`` adds the measurements that take runs of
+their own (clock run, exact-f32 kernel, CPU baseline), the committed PMC
+summary and the df_comm check of the forward mode.  Extra objects:
   roofline     — the fused kernel against the f32 MFMA peak (it is compute-
                  bound: 3,212 FLOP/B algorithmic intensity); achieved = 2·ΣMAC
                  per sample × samples per launch ÷ mean launch time from HIP
                  events on the launch stream.
-  cpu_baseline — the C++/OpenMP fp32 restatement of the reference's CPU
+  cpu_baseline — (--full) the C++/OpenMP fp32 restatement of the reference's CPU
                  forward (oracle/cpu_flow.cpp: Flux's unfused Dense order,
                  register-blocked GEMMs, one sample block per thread), pinned
                  to the numpy oracle by tests/test_oracle.py, timed on the
@@ -259,13 +263,22 @@ def main():
     ap.add_argument("--mode", choices=["forward", "nll", "train"], default="forward")
     ap.add_argument("--config", choices=sorted(CONFIGS), default="cfg2",
                     help="cfg2 is the headline (BASELINE configs[1]); cfg1/cfg4 are secondary measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the secondary measurements: the clock run, the exact-f32 "
+                         "kernel timing, the CPU baseline, the committed PMC summary and (forward mode) the df_comm "
+                         "check; --no-cpu / --no-exact / --no-clock drop one of them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy (rank 0; "
+                         "f32 / f64, at most 64 MB in all: a fixed seeded sample of a larger output). Inputs are "
+                         "seeded, so two builds compare output for output. Train mode runs no settle steps then "
+                         "(their number depends on the time and the weights move with every step)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-exact", action="store_true",
-                    help="skip the exact-f32 FAST kernel timing that accompanies a SPLIT-kernel bench")
+                    help="with --full: skip the exact-f32 FAST kernel timing that accompanies a SPLIT-kernel bench")
     ap.add_argument("--no-clock", action="store_true",
-                    help="skip the clock run: a separate run of launches after the timed loop with the in-kernel "
-                         "clock stamps on (df_chain_clock_probe); the timed launches never carry stamps")
+                    help="with --full: skip the clock run: a separate run of launches after the timed loop with the "
+                         "in-kernel clock stamps on (df_chain_clock_probe); the timed launches never carry stamps")
     ap.add_argument("--settle-seconds", type=float, default=0.3,
                     help="untimed steps after the W warm-up steps until this much warm-up time has passed "
                          "(DVFS clock ramp; 0 = exactly W)")
@@ -274,6 +287,10 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous / timing plumbing only: no library, no GPU work (CPU tests)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.mode == "train":
+        args.settle_seconds = 0.0
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))
@@ -325,10 +342,10 @@ def main():
     comm_error = None
     probe = hc                       # the handle whose chain-pass launches carry the clock stamps
     rehearsal = dist is not None and dist.get_backend() != "nccl"   # gloo: ranks may share one GPU
-    if not rehearsal:
+    if not rehearsal and (args.mode != "forward" or args.full):
         # the library's own RCCL communicator (df_comm) carries every exchange of the
         # nll / train steps, at every rank count (world 1 included).  The forward step has
-        # no exchange; there it only carries the per-rank report after the timed loop, and a
+        # no exchange; there (--full only) it carries the per-rank report after the timed loop, and a
         # failure to build it is reported in the line instead of ending the run
         from densityflows_amd.parallel import DFComm
 
@@ -435,8 +452,17 @@ def main():
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     gpu_ms = ev0.elapsed_time(ev1)                 # HIP events on the launch stream
+    if args.dump_outputs and rank == 0:
+        # before anything below launches again into the same buffers
+        if args.mode == "forward":
+            outs = {"x": xbuf, "ldj": ldj}
+        elif args.mode == "nll":
+            outs = {"logpdf_sum_count": s64}
+        else:
+            outs = {"logpdf_sum": s64[:1], "grad": trainer.grad(), "params": trainer.get_params()}
+        dump_outputs(args.dump_outputs, outs)
     clock = None
-    if not args.no_clock:
+    if args.full and not args.no_clock:
         # the clock run: the same steps right after the timed loop (the chip still at its
         # steady clock) with the in-kernel stamps on; the timed launches above ran the plain
         # production kernels
@@ -494,7 +520,7 @@ def main():
         peak = f_all / (f_split / PEAK_SPLIT_TFLOPS + (f_all - f_split) / PEAK_F32_TFLOPS)
 
     exact = None
-    if kernel_id in (4, 6) and args.mode == "forward" and not args.no_exact:
+    if args.full and kernel_id in (4, 6) and args.mode == "forward" and not args.no_exact:
         # the same launches on the exact-f32 kernel: a second handle planned under
         # DF_F32_EXACT=1 (a chain's arithmetic is fixed when it is created)
         from densityflows_amd.hip import HIPChain
@@ -524,7 +550,7 @@ def main():
 
     traffic, traffic_src, pmc = None, None, {}
     default_b = (1 << 18) if args.config == "cfg4" else (1 << 20)
-    if args.config in TRAFFIC_PROFILES and args.mode == "forward" and B == default_b:
+    if args.full and args.config in TRAFFIC_PROFILES and args.mode == "forward" and B == default_b:
         traffic_src = TRAFFIC_PROFILES[args.config]
         pmc = pmc_summary(traffic_src)
         traffic = pmc["traffic"]
@@ -579,7 +605,7 @@ def main():
             out["metric"] = out["metric"].replace("d=5 8-layer RealNVP", CONFIGS[args.config][2].split(":")[0])
         if exact is not None:
             out["f32_exact_kernel"] = exact
-        if world == 1 and not args.no_cpu and args.mode == "forward":
+        if args.full and world == 1 and not args.no_cpu and args.mode == "forward":
             # config 1 is the reference's CPU case at B = 4096 (BASELINE configs[0])
             out["cpu_baseline"] = cpu_baseline(chain, d, n, seconds=args.cpu_seconds,
                                                sample=4096 if args.config == "cfg1" else 65536)
@@ -592,6 +618,33 @@ def main():
         comm.close()
     if dist is not None:
         dist.destroy_process_group()
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, outs):
+    """DIR/<name>.npy of the arrays a caller of the timed path receives (f32 / f64 as
+    computed).  Above DUMP_BYTES in all, every array is cut to the same fraction of its
+    elements, at sorted indices drawn from a fixed seed (the indices depend on the
+    arrays' lengths alone)."""
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    arrs = {}
+    for k, v in outs.items():
+        a = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        arrs[k] = np.ascontiguousarray(a).reshape(-1)
+    total = sum(a.nbytes for a in arrs.values())
+    for k, a in arrs.items():
+        if total > DUMP_BYTES:
+            keep = max(1, int(a.size * (DUMP_BYTES / total)))
+            if keep < a.size:
+                idx = np.sort(np.random.default_rng(12345).choice(a.size, keep, replace=False))
+                a = a[idx]
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def rank_report(dist, dev, kernel_ms, wall_ms, world, batch, comm, comm_error, group_desc):

@@ -16,7 +16,7 @@ if [ -n "${TESTLIB:-}" ]; then
 fi
 for rep in 1 2; do
   for lib in "$@"; do
-    DENSITYFLOWS_HIP_LIB=densityflows.jl_amd/$lib timeout -k 10 300 python3 bench.py $ARGS --no-cpu --no-exact \
+    DENSITYFLOWS_HIP_LIB=densityflows.jl_amd/$lib timeout -k 10 300 python3 bench.py $ARGS --full --no-cpu --no-exact \
         > $O/${lib%.so}_$rep.json 2> $O/${lib%.so}_$rep.err || exit 1
   done
 done

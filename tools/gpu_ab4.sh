@@ -16,7 +16,7 @@ run() {  # <name> <lib> <rep> <bench args>   (lib "env": the in-tree build under
   local so=$2 tag=${2%.so} envs=""
   if [ "$2" = env ]; then so=libdensityflows_hip.so; envs="$ABENV"; fi
   if [ "$2" = env2 ]; then so=libdensityflows_hip.so; envs="$ABENV2"; fi
-  env $envs DENSITYFLOWS_HIP_LIB=densityflows.jl_amd/$so timeout -k 10 300 python3 bench.py $4 --no-cpu \
+  env $envs DENSITYFLOWS_HIP_LIB=densityflows.jl_amd/$so timeout -k 10 300 python3 bench.py $4 --full --no-cpu \
       > $O/$1_${tag}_$3.json 2> $O/$1_${tag}_$3.err
 }
 for rep in $(seq 1 ${REPS:-2}); do

@@ -17,19 +17,19 @@ echo "pytest rc $rc" >> $O/pytest_gpu.log
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 timeout -k 10 240 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 && \
 timeout -k 10 240 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err && \
-timeout -k 10 240 python3 bench.py --steps 200 --warmup 50 --cpu-seconds 15 > $O/bench.json 2> $O/bench.err && \
+timeout -k 10 240 python3 bench.py --steps 200 --warmup 50 --full --cpu-seconds 15 > $O/bench.json 2> $O/bench.err && \
 timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_driver -o run -- \
     python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/prof_driver.log 2>&1 && \
 timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- \
     python3 bench.py --no-cpu > $O/prof.log 2>&1 && \
-timeout -k 10 240 python bench.py --config cfg1 --batch 4096 --steps 500 --warmup 100 --cpu-seconds 10 > $O/cfg1_4096.json 2> $O/cfg1_4096.err && \
-timeout -k 10 240 python bench.py --config cfg1 --steps 200 --warmup 50 --cpu-seconds 10 > $O/cfg1.json 2> $O/cfg1.err && \
-timeout -k 10 240 python bench.py --config cfg4 --steps 20 --warmup 10 --cpu-seconds 15 > $O/cfg4.json 2> $O/cfg4.err && \
+timeout -k 10 240 python bench.py --config cfg1 --batch 4096 --steps 500 --warmup 100 --full --cpu-seconds 10 > $O/cfg1_4096.json 2> $O/cfg1_4096.err && \
+timeout -k 10 240 python bench.py --config cfg1 --steps 200 --warmup 50 --full --cpu-seconds 10 > $O/cfg1.json 2> $O/cfg1.err && \
+timeout -k 10 240 python bench.py --config cfg4 --steps 20 --warmup 10 --full --cpu-seconds 15 > $O/cfg4.json 2> $O/cfg4.err && \
 timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_cfg4 -o run -- \
     python3 bench.py --config cfg4 --steps 10 --warmup 3 --no-cpu > $O/prof_cfg4.log 2>&1 && \
-timeout -k 10 240 python bench.py --mode nll --steps 100 --warmup 20 > $O/nll.json 2> $O/nll.err && \
-timeout -k 10 240 python bench.py --mode train --steps 20 --warmup 5 > $O/train_cfg2.json 2> $O/train_cfg2.err && \
-timeout -k 10 300 python bench.py --mode train --config cfg4 --steps 5 --warmup 2 > $O/train_cfg5.json 2> $O/train_cfg5.err && \
+timeout -k 10 240 python bench.py --full --mode nll --steps 100 --warmup 20 > $O/nll.json 2> $O/nll.err && \
+timeout -k 10 240 python bench.py --full --mode train --steps 20 --warmup 5 > $O/train_cfg2.json 2> $O/train_cfg2.err && \
+timeout -k 10 300 python bench.py --full --mode train --config cfg4 --steps 5 --warmup 2 > $O/train_cfg5.json 2> $O/train_cfg5.err && \
 timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_t2 -o run -- \
     python3 bench.py --mode train --steps 10 --warmup 3 > $O/prof_t2.log 2>&1 && \
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_t5 -o run -- \

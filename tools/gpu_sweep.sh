@@ -13,7 +13,7 @@ grep "\[df\]" $O/debug.err | sort | uniq -c | head -5
 for rep in 1 2; do
   for v in "" "DF_TILES=2" "DF_TILES=4" "DF_TILES=6" "DF_TILES=8" "DF_SPLIT_LDS_KB=48" "DF_SPLIT_LDS_KB=96"; do
     tag=${v:-default}
-    env $v timeout -k 10 120 python3 bench.py --steps 200 --warmup 50 --no-cpu --no-exact \
+    env $v timeout -k 10 120 python3 bench.py --steps 200 --warmup 50 --full --no-cpu --no-exact \
         > $O/${tag}_$rep.json 2> $O/${tag}_$rep.err || exit 1
   done
 done
