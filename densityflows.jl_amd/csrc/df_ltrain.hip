@@ -14,8 +14,9 @@ using impl::mfma4;
 
 // 8 values (two f32x4 of a lane, a then b) → their bf16x3 planes on the VALU (uni::split8:
 // v_mov + v_dot2c per remainder).  DF_LT_MREM=1: the remainders on the matrix pipe
-// (uni::split8_mrem, one v_mfma_f32_16x16x16_bf16 with A = −I per 4 values: an exact
+// (uni::split8_mrem, one v_mfma_f32_4x4x4_16b_bf16 with A = −I per 4 values: an exact
 // element-wise x − hi for any 4 values of a lane), bitwise the same planes; measured slower
+// in its earlier 16-wide form, v_mfma_f32_16x16x16_bf16 (not re-measured with the 4x4x4 one)
 // here (config-5 step 34.2 vs 33.4 ms, gpurun_out/r05m)
 #ifndef DF_LT_MREM
 #define DF_LT_MREM 0

@@ -436,13 +436,20 @@ __device__ __forceinline__ void split8(const float (&v)[8], bf16x8& p0, bf16x8& 
 
 // Remainders on the matrix pipe (DF_SPLIT_MREM): for one accumulator tile c (lane
 // (g, j): rows 4g + r of sample j) and its RNE bf16 plane h (the same four values),
-// v_mfma_f32_16x16x16_bf16 with A = −I and C = c gives c − h: the only non-zero
-// product is −h, exact, and C + one product rounds once — to the exact difference
-// (representable: h is c rounded to 8 significant bits).  Bitwise the dot2 remainder,
-// one matrix instruction per 16 values instead of 16 v_dot2c_f32_bf16 (which cost
-// ≈ 8–10 issue cycles each beside the MFMAs).  −I on the A operand: lane (g, i) holds
-// A[i][4g + e], −1 iff 4g + e == i.  (A non-finite value of one row turns 0·inf into
-// NaN for its whole sample — whose outputs are non-finite anyway.)
+// v_mfma_f32_4x4x4_16b_bf16 with A = −I in each of its 16 independent 4×4 blocks and
+// C = c gives c − h: the only non-zero product is −h, exact, and C + one product
+// rounds once — to the exact difference (representable: h is c rounded to 8
+// significant bits).  Bitwise the dot2 remainder, one matrix instruction per 256
+// values instead of 256 lanes' v_dot2c_f32_bf16 (which cost ≈ 8–10 issue cycles each
+// beside the MFMAs), and 2 matrix-pipe passes where the 16-wide contraction
+// (v_mfma_f32_16x16x16_bf16, A = −I) took 4: 8.6 against 16.1 cycles alone, 15.5
+// against 22.7 beside a product MFMA (tools/probe/mfma_rem.hip).  The subtraction
+// is lane-local: lane l holds row l%4 of its block's A, column l%4 of B (its four
+// bf16) and column l%4 of C/D (its four f32), so with A's row l%4 = −1 at element
+// l%4 and 0 elsewhere D[e] = C[e] − B[e] in the lane's own registers, whichever
+// accumulator layout the tile is in.  (A non-finite value turns 0·inf into NaN for
+// its own lane's four values only — four rows of the same sample, whose outputs are
+// non-finite anyway.)
 #ifndef DF_SPLIT_MREM
 #define DF_SPLIT_MREM 1
 #endif
@@ -450,15 +457,15 @@ typedef short short4v __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ short4v neg_eye() {
-    const int lane = threadIdx.x & 63, i = lane & 15, g = lane >> 4;
+    const int i = threadIdx.x & 3;
     short4v p;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) p[e] = (4 * g + e == i) ? (short)0xbf80 : (short)0;
+    for (int e = 0; e < 4; ++e) p[e] = (e == i) ? (short)0xbf80 : (short)0;
     return p;
 }
 
 __device__ __forceinline__ f32x4 mrem(short4v eye, bf16x4v h, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(eye, __builtin_bit_cast(short4v, h), c, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(eye, __builtin_bit_cast(short4v, h), c, 0, 0, 0);
 }
 
 // planes of two accumulator tiles (8 values: a then b), remainders on the matrix pipe

@@ -429,8 +429,9 @@ __device__ __forceinline__ f32x4 add_hilo(const f32x4& a, const f32x4& b) {
 
 // Planes of accumulator tiles 2c, 2c+1 (inputs 32c + 16(e>>2) + 4g + (e&3)).
 // DF_WIDE_MREM: the remainders on the matrix pipe (uni::split8_mrem, bitwise split8).  Off:
-// this kernel is matrix-pipe bound at one wave per SIMD, and the extra 16x16x16 MFMAs cost
-// more than the v_dot2c they replace (config-4 forward 35.7 vs 37.3 Msamples/s).
+// this kernel is matrix-pipe bound at one wave per SIMD, and the extra MFMAs (measured in
+// their earlier 16x16x16 form; now v_mfma_f32_4x4x4_16b_bf16) cost more than the v_dot2c
+// they replace (config-4 forward 35.7 vs 37.3 Msamples/s).
 #ifndef DF_WIDE_MREM
 #define DF_WIDE_MREM 0
 #endif
