@@ -13,7 +13,7 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libdensityflows_hip.so")
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 # df_status
 DF_OK = 0
@@ -138,6 +138,7 @@ SIGNATURES = {
     "df_train_sweep": (C.c_int, [_VP, C.POINTER(C.c_int)]),
     "df_train_num_params": (C.c_int, [_VP, C.POINTER(_I64)]),
     "df_train_gradient": (C.c_int, [_VP, _VP, _VP, _I64, _I64, _VP, _VP]),
+    "df_train_logpdf_grad": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP]),
     "df_train_grad_ptr": (C.c_int, [_VP, C.POINTER(_VP)]),
     "df_train_apply": (C.c_int, [_VP, _VP]),
     "df_train_step": (C.c_int, [_VP, _VP, _VP, _I64, _VP, _VP]),

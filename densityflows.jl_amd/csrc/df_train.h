@@ -126,4 +126,45 @@ hipError_t launch_repack(float* blob, const int32_t* dst, const int32_t* src, in
 hipError_t launch_repack_split(uint8_t* blob, const int32_t* dst, const int32_t* src, int64_t count,
                                const float* params, hipStream_t st);
 
+// ---- per-sample input gradients of logpdf (df_train_logpdf_grad; df_score_impl.h) ----
+// The same sweep as the trainer's with the seed z̄ = -z, j̄ = 1 and no reduction over the
+// batch: score_net_kernel recomputes one conditioner (exact f32, GNet::u), applies the
+// coupling pullback and back-propagates to the conditioner input; its rows go to z̄
+// (identity dims) and, new here, to θ̄ (θ slots).  No dW / db, no LDS transposes.
+// 4 waves per workgroup, one 16-sample tile each and one wave per SIMD: the hidden-64
+// instances hold 157-168 VGPRs, 3 waves per SIMD, which an 8-wave workgroup (2 per SIMD)
+// cannot fill
+constexpr int kScoreWaves = 4;
+constexpr int kScoreThreads = 64 * kScoreWaves;
+
+struct ScoreArgs {
+    const float* u_in;       // U[li+1]: the layer's input in the inverse pass
+    const float* u_out;      // U[li]:   its output
+    const float* theta;
+    const float* tmin;       // θ bounds (nullptr: θ used as given)
+    const float* tmax;
+    const int32_t* feat;     // [16] state slot of conditioner feature k (n + d → zero)
+    const int32_t* af;       // [n_af] state slots of the transformed dims
+    float* zbar;             // [sample][d] adjoint of the layer output, updated in place
+    float* thbar;            // [sample][n] adjoint of the (normalised) θ, added to in place; may be nullptr
+    float* ebuf;             // [sample][4] exp(-s) from the s-net launch
+    const uint8_t* blob;     // chain weight blob (forward fragments)
+    const uint8_t* tblob;    // transposed fragments
+    int64_t batch;
+    int d, n, n_af, kind, phase;
+    GNet net;                // the net of this launch; pair launches: the layer's s-net
+    GNet net2;               // pair launches (one per RNVP layer): its t-net
+};
+
+inline size_t score_net_lds(const GNet& g) { return (size_t)g.fwd_bytes + (size_t)g.t_bytes; }
+constexpr size_t kScoreLdsMax = 160 * 1024;    // LDS of a gfx950 workgroup
+// (sets the instance's MaxDynamicSharedMemorySize to the largest lds it has been launched with)
+// pair: one launch runs a.net (s) then a.net2 (t) of an RNVP layer; lds holds both
+hipError_t launch_score_net(int ht, int nh, int am, bool pair, const ScoreArgs& a, unsigned grid, size_t lds,
+                            hipStream_t st);
+hipError_t score_net_occupancy(int ht, int nh, int am, bool pair, size_t lds, int* blocks);
+// gθ[j][i] = θ̄[j][i] / (θmax[i] - θmin[i]), 0 where θmax == θmin (normalize_input's constant rows)
+hipError_t launch_score_theta_raw(float* gth, const float* tmin, const float* tmax, int n, int64_t batch,
+                                  hipStream_t st);
+
 }  // namespace df

@@ -27,6 +27,15 @@ struct SweepOp {
     int phase;   // TR_PHASE_S / TR_PHASE_T
 };
 
+// One launch of df_train_logpdf_grad's sweep.
+struct ScoreOp {
+    int layer;   // index in plan.layers
+    int net;     // index in df_train::nets (pair: the s-net), -1 for a NormalizationLayer
+    int net2;    // pair: the t-net, else -1
+    int phase;
+    size_t lds;
+};
+
 int round16(int v) { return (v + 15) / 16 * 16; }
 
 int pow2_tiles(int rows) {
@@ -113,6 +122,11 @@ struct df_train {
     int64_t cap = 0;       // batch capacity of snap / zbar / ebuf
     int grid = 0;          // workgroups of a full net launch (resident on the device)
     size_t lds_max = 0;
+    // df_train_logpdf_grad (score_net_kernel), planned on the first call: one launch per
+    // RNVP layer (both nets) where that fits, else per net; resident workgroups
+    std::vector<ScoreOp> score_ops;
+    int score_grid = 0;
+    bool score_per_net = false;       // DF_SCORE_PER_NET=1 at df_train_create: per-net launches only (A/B)
     // layer-wise path (hidden width > 64, deep or wide-output conditioners)
     bool layerwise = false;
     std::vector<LNet> lnets;
@@ -970,6 +984,7 @@ int df_train_create_ex(df_train** out, df_chain* c, const df_adam* opt, int swee
     t->c = c;
     t->sweep_req = form;
     t->separate = (sweep & DF_SWEEP_SEPARATE) != 0;
+    if (const char* v = std::getenv("DF_SCORE_PER_NET")) t->score_per_net = v[0] == '1';
     t->opt = opt ? *opt : df_adam{1e-3f, 0.9f, 0.999f, 1e-8f};
     if (!(t->opt.eta >= 0.f) || !(t->opt.beta1 >= 0.f && t->opt.beta1 < 1.f) ||
         !(t->opt.beta2 >= 0.f && t->opt.beta2 < 1.f) || !(t->opt.epsilon >= 0.f)) {
@@ -1226,6 +1241,126 @@ int df_train_gradient(df_train* t, const float* x, const float* theta_raw, int64
     // 4. fixed-order reduction of the workgroup partials
     e = launch_reduce_grads(t->d_partial, grid, t->P, t->d_grad, st);
     return e == hipSuccess ? DF_OK : hip_err(e, "gradient reduction launch");
+}
+
+int df_train_logpdf_grad(df_train* t, const float* x, const float* theta, float* logpdf_out, float* grad_x,
+                         float* grad_theta, int64_t batch, void* stream) {
+    if (!t) return set_err(DF_ERR_INVALID, "null trainer");
+    if (batch < 0) return set_err(DF_ERR_SHAPE, "negative batch size");
+    if (t->layerwise)
+        return set_err(DF_ERR_UNSUPPORTED,
+                       "df_train_logpdf_grad needs a trainer on the fused sweep; this chain trains layer-wise "
+                       "(a conditioner with hidden width > 64, more than one hidden Dense, or more than 4 "
+                       "transformed dims in a layer)");
+    if (batch == 0) return DF_OK;
+    if (!x) return set_err(DF_ERR_INVALID, "null input array");
+    df_chain* c = t->c;
+    const Plan& P = c->plan;
+    if (P.n > 0 && !theta)
+        return set_err(DF_ERR_SHAPE, "dimensions θ must match (n, dims...) with n number of trained parameters");
+    const int tf = theta_flow(t);
+    if (tf < 0) return set_err(DF_ERR_INVALID, "θ bounds not set (df_chain_set_theta_bounds) for DF_THETA_RAW");
+    const bool flow = tf == 1;
+    if (P.n == 0) grad_theta = nullptr;
+    DeviceGuard gd(c->device);
+    if (!gd.ok) return set_err(DF_ERR_HIP, "hipSetDevice failed");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!grad_x && !grad_theta) {  // logpdf alone: the inverse pass without the kept outputs
+        if (!logpdf_out) return DF_OK;
+        return run(c, MODE_LOGPDF, flow, x, theta, nullptr, nullptr, logpdf_out, nullptr, batch, stream);
+    }
+    if (t->score_grid == 0) {  // plan the launches: LDS against the workgroup's limit, resident grid
+        std::vector<ScoreOp> plan;
+        int occ = 0;
+        for (size_t i = 0; i < t->ops.size(); ++i) {
+            const SweepOp& op = t->ops[i];
+            ScoreOp so{op.layer, op.net, -1, op.phase, 0};
+            if (op.net >= 0) {
+                so.lds = score_net_lds(t->nets[op.net]);
+                if (so.lds > kScoreLdsMax)
+                    return set_err(DF_ERR_UNSUPPORTED,
+                                   "df_train_logpdf_grad: a conditioner needs more than 160 KiB of LDS");
+                // an RNVP layer's s-net and t-net (consecutive ops) of the same depth: one launch
+                if (!t->score_per_net && op.phase == TR_PHASE_S && i + 1 < t->ops.size() &&
+                    t->ops[i + 1].layer == op.layer && t->ops[i + 1].net >= 0 &&
+                    t->net_nh[t->ops[i + 1].net] == t->net_nh[op.net] &&
+                    so.lds + score_net_lds(t->nets[t->ops[i + 1].net]) <= kScoreLdsMax) {
+                    so.net2 = t->ops[i + 1].net;
+                    so.lds += score_net_lds(t->nets[so.net2]);
+                    ++i;
+                }
+                int b = 0;
+                hipError_t eo = score_net_occupancy(P.ht, t->net_nh[so.net], t->amode, so.net2 >= 0, so.lds, &b);
+                if (eo != hipSuccess) return hip_err(eo, "hipOccupancyMaxActiveBlocksPerMultiprocessor(score)");
+                occ = occ == 0 ? b : std::min(occ, b);
+            }
+            plan.push_back(so);
+        }
+        t->score_ops.swap(plan);
+        t->score_grid = std::max(1, c->n_cu * std::max(1, occ));
+        if (c->debug_launch)
+            std::fprintf(stderr, "[df] logpdf_grad: %zu launches (%s), %d workgroups of %d waves per CU, grid %d\n",
+                         t->score_ops.size(), t->score_per_net ? "per net" : "per layer", occ, kScoreWaves,
+                         t->score_grid);
+    }
+    int rc = ensure_capacity(t, batch);
+    if (rc != DF_OK) return rc;
+
+    // 1. inverse pass keeping every layer's output (U[li] = snap[li], U[0] = z); lp per sample
+    rc = run(c, MODE_LOGPDF, flow, x, theta, nullptr, nullptr, logpdf_out, nullptr, batch, stream, t->d_snap);
+    if (rc != DF_OK) return rc;
+    const int64_t bd = batch * P.d;
+    // 2. z̄ = ∂logpdf(MvNormal(0,I), z)/∂z = -z.  grad_x has z̄'s layout ([sample][d]): the
+    //    sweep runs in it, and what is left after the last layer is ∂lp/∂x
+    float* zbar = grad_x ? grad_x : t->d_zbar;
+    hipError_t e = launch_scale(zbar, t->d_snap, -1.f, bd, st);
+    if (e != hipSuccess) return hip_err(e, "scale kernel launch");
+    // θ̄ accumulates in grad_theta ([sample][n]) over the nets that read θ
+    if (grad_theta) {
+        e = hipMemsetAsync(grad_theta, 0, sizeof(float) * (size_t)batch * P.n, st);
+        if (e != hipSuccess) return hip_err(e, "hipMemsetAsync");
+    }
+    // 3. reverse sweep, chain order
+    const int64_t ntiles = (batch + 15) / 16;
+    const int grid = (int)std::min<int64_t>(t->score_grid, (ntiles + kScoreWaves - 1) / kScoreWaves);
+    for (const ScoreOp& op : t->score_ops) {
+        const DevLayer& L = P.layers[op.layer];
+        if (op.net < 0) {
+            const float* xmn = static_cast<const float*>(c->d_params) + L.norm_off;
+            e = launch_norm_adjoint(zbar, xmn, xmn + P.d, L.alpha, L.beta, P.d, batch, st);
+            if (e != hipSuccess) return hip_err(e, "norm adjoint launch");
+            continue;
+        }
+        ScoreArgs a{};
+        a.u_in = (op.layer + 1 < P.n_layers) ? t->d_snap + (int64_t)(op.layer + 1) * bd : x;
+        a.u_out = t->d_snap + (int64_t)op.layer * bd;
+        a.theta = theta;
+        a.tmin = flow ? c->d_bounds : nullptr;
+        a.tmax = flow ? c->d_bounds + P.n : nullptr;
+        a.feat = static_cast<const int32_t*>(c->d_tables) + L.feat_tab;
+        a.af = static_cast<const int32_t*>(c->d_tables) + L.af_tab;
+        a.zbar = zbar;
+        a.thbar = grad_theta;
+        a.ebuf = t->d_ebuf;
+        a.blob = static_cast<const uint8_t*>(c->d_blob);
+        a.tblob = static_cast<const uint8_t*>(t->d_tblob);
+        a.batch = batch;
+        a.d = P.d;
+        a.n = P.n;
+        a.n_af = L.n_af;
+        a.kind = L.kind;
+        a.phase = op.phase;
+        a.net = t->nets[op.net];
+        if (op.net2 >= 0) a.net2 = t->nets[op.net2];
+        e = launch_score_net(P.ht, t->net_nh[op.net], t->amode, op.net2 >= 0, a, (unsigned)grid, op.lds, st);
+        if (e != hipSuccess) return hip_err(e, "score kernel launch");
+    }
+    // 4. raw θ: the chain rule of normalize_input
+    if (grad_theta && flow) {
+        e = launch_score_theta_raw(grad_theta, c->d_bounds, c->d_bounds + P.n, P.n, batch, st);
+        if (e != hipSuccess) return hip_err(e, "θ gradient scaling launch");
+    }
+    return DF_OK;
 }
 
 int df_train_apply(df_train* t, void* stream) {

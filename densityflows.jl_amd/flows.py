@@ -13,8 +13,8 @@ from .chains import FlowChain, _n_of
 from .data import DataArrays, MetaData, maximum_theta, minimum_theta
 from .hip import as_julia_device, julia_empty
 
-__all__ = ["Flow", "MvNormal", "predict", "sample", "logpdf", "pdf", "training_loss", "validation_loss",
-           "nll_partial_sum"]
+__all__ = ["Flow", "MvNormal", "predict", "sample", "logpdf", "logpdf_grad", "pdf", "training_loss",
+           "validation_loss", "nll_partial_sum"]
 
 LOG2PI = float(np.log(2.0 * np.pi))
 
@@ -149,6 +149,50 @@ def logpdf(flow: Flow, x, theta=None):
     """``logpdf(flow, x, θ)`` — src/Flows.jl:272-284: backward + base logpdf + ldj (fused)."""
     th = flow._theta(theta, x)
     return flow.hip().logpdf(x, th)
+
+
+def logpdf_grad(flow: Flow, x, theta=None, state=None):
+    """``(lp, gx, gθ)``: ``logpdf(flow, x, θ)`` per point and its gradients in ``x`` and in the
+    raw ``θ`` — what ``Zygote.gradient((x, θ) -> sum(logpdf(flow, x, θ)), x, θ)`` gives in the
+    reference through ``rrule(RNVP_backward)`` (src/affine/RNVP.jl:137-141) and the θ
+    normalisation (``grad_normalisation``, src/Data.jl:236-241).  One library call
+    (``df_train_logpdf_grad``).  Shapes (dims...), (d, dims...), (n, dims...); numpy in, numpy
+    out; an NTuple θ is broadcast and ``gθ`` returned per point.  ``state``: a
+    :class:`TrainState` whose trainer (and current parameters) is used; without it a
+    temporary trainer is created and destroyed inside the call."""
+    import torch
+
+    from .hip import HIPChain, _to_numpy
+    from .train import Adam, HIPTrainer
+
+    th = flow._theta(theta, x)
+    if state is not None:
+        tr, h = state.trainer, state.trainer.chain
+    else:
+        h = flow.hip()
+        # A new trainer starts from the parameters the chain was planned with: hand the chain
+        # the model's current ones first.  The library refuses that while another trainer is
+        # bound to the chain (it may hold newer parameters than the model): pass it as `state`.
+        try:
+            h.set_weights(flow.model.layers)
+        except _lib.ArgumentError as e:
+            raise _lib.ArgumentError(f"logpdf_grad: the flow has a live TrainState, pass it as state= ({e})") from e
+        tr = HIPTrainer(h, Adam())
+    try:
+        xb, thb, dims, batch, was_np = h._inputs(x, th, "x")
+        lpb = torch.empty(batch, dtype=torch.float32, device=h.device)
+        gxb, gxv = julia_empty(h.d, dims, h.device)
+        gtb, gtv = julia_empty(h.n, dims, h.device)
+        tr.logpdf_grad(xb, thb, batch, lpb, gxb, gtb if h.n > 0 else None)
+        lpv = HIPChain._ldj_view(lpb, dims)
+        if state is None:
+            torch.cuda.synchronize(h.device)
+    finally:
+        if state is None:
+            tr.close()
+    if was_np:
+        return _to_numpy(lpv), _to_numpy(gxv), _to_numpy(gtv)
+    return lpv, gxv, gtv
 
 
 def pdf(flow: Flow, x, theta=None):

@@ -52,7 +52,7 @@ export HIPFlowChain, HIPTrainer, HIPComm, train_step!, train_step_graph!, train_
        copy_trainables!, hip_flow, flow_nll, sample
 
 const LIB = get(ENV, "DENSITYFLOWS_HIP_LIB", joinpath(@__DIR__, "..", "libdensityflows_hip.so"))
-const ABI_VERSION = Int32(4)
+const ABI_VERSION = Int32(5)
 
 function __init__()
     v = ccall((:df_get_abi_version, LIB), Cint, ())

@@ -79,7 +79,8 @@ class HIPTrainer:
         _lib.check(self.lib.df_train_num_params(self.handle, C.byref(n)))
         self.num_params = int(n.value)
 
-    def __del__(self):
+    def close(self) -> None:
+        """df_train_destroy now (the chain then accepts df_chain_set_weights again)."""
         h = getattr(self, "handle", None)
         if h is not None and h.value:
             try:
@@ -88,9 +89,19 @@ class HIPTrainer:
                 pass
             self.handle = None
 
+    def __del__(self):
+        self.close()
+
     @property
     def device(self):
         return self.chain.device
+
+    def logpdf_grad(self, xbuf, thbuf, batch: int, lp=None, gx=None, gth=None):
+        """df_train_logpdf_grad on flat device buffers: per-sample logpdf → ``lp`` (batch,),
+        ∂logpdf/∂x → ``gx`` (batch·d, Julia order), ∂logpdf/∂θ → ``gth`` (batch·n); each may be
+        None.  θ is read as ``set_theta_input`` says; the trainer's state is left as it is."""
+        _lib.check(self.lib.df_train_logpdf_grad(self.handle, _ptr(xbuf), _ptr(thbuf), _ptr(lp), _ptr(gx), _ptr(gth),
+                                                 C.c_int64(batch), _stream(self.device)), "df_train_logpdf_grad")
 
     def grad(self):
         """The flat gradient as a torch tensor aliasing the device buffer."""

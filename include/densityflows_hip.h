@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define DF_ABI_VERSION 4
+#define DF_ABI_VERSION 5
 
 typedef enum df_status {
     DF_OK = 0,
@@ -322,6 +322,29 @@ int df_train_set_theta_input(df_train* t, int mode);
  * at the current parameters (the loss before the update is -Σ/n_total). */
 int df_train_gradient(df_train* t, const float* x, const float* theta_raw, int64_t batch, int64_t n_total,
                       double* logpdf_sum, void* stream);
+/* Per-sample gradients of the log-density in its inputs (ABI 5), at the trainer's
+ * current parameters.  For every sample j:
+ *   logpdf_out[j]      = logpdf(MvNormal(0,I), z_j) + ldj_j,  (z, ldj) = backward(chain, x, θ)
+ *   grad_x[:, j]       = ∂logpdf_out[j] / ∂x[:, j]       (d, batch), column-major like x
+ *   grad_theta[:, j]   = ∂logpdf_out[j] / ∂θ[:, j]       (n, batch), column-major like θ
+ * which is Zygote.gradient((x, θ) -> sum(logpdf(flow, x, θ)), x, θ) through
+ * rrule(RNVP_backward) / rrule(NICE_backward) (src/affine/RNVP.jl:137-141,
+ * NICE.jl:102-111).  Each output may be NULL and is then not written; grad_theta is
+ * ignored when n = 0.  θ is read as df_train_set_theta_input says, like
+ * df_train_gradient; when it is raw (normalised in the kernels with the chain's bounds)
+ * grad_theta is the gradient in the raw θ: θ̄ / (θmax - θmin), and exactly 0 in a row
+ * with θmax == θmin (grad_normalisation, src/Data.jl:236-241).
+ * The call changes neither the parameters, the Adam state, the gradient of
+ * df_train_gradient nor its Σ logpdf: df_train_gradient → df_train_logpdf_grad →
+ * df_train_apply applies the same step as without the middle call.  It is stream-ordered
+ * and bitwise reproducible.  grad_x and grad_theta serve as the sweep's workspace while
+ * the call runs on the stream.
+ * Only trainers on the fused sweep (df_train_sweep: DF_SWEEP_FUSED) are supported.  For a
+ * layer-wise trainer (a conditioner with hidden width > 64, more than one hidden Dense,
+ * or more than 4 transformed dims in a layer) the call returns DF_ERR_UNSUPPORTED and the
+ * trainer stays usable.  batch == 0: DF_OK, nothing written. */
+int df_train_logpdf_grad(df_train* t, const float* x, const float* theta, float* logpdf_out, float* grad_x,
+                         float* grad_theta, int64_t batch, void* stream);
 /* Device pointer of the flat gradient (count floats); all-reduce it here
  * for multi-GPU data parallelism. */
 int df_train_grad_ptr(df_train* t, float** grad_dev);
