@@ -131,25 +131,35 @@ __device__ __forceinline__ T cload(const T* p, int64_t i) {
     return *(const T*)(&((CT*)(uintptr_t)p)[i]);
 }
 
+// LANE_LOCAL: the lane's byte offset is derived here from an opaque copy of the thread id,
+// so the source address is a scalar base plus one short-lived VGPR; otherwise the compiler
+// keeps a.blob + 16·lane in a VGPR pair for the whole kernel (spilled in the FAST SPLIT
+// logpdf instance at 128 VGPRs).
+template <bool LANE_LOCAL = false>
 __device__ __forceinline__ void dma_stage(const ChainArgs& a, int s, uint8_t* dst) {
     const DevStage st = cload(a.stages, s);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    uint32_t loff = lane * 16;
+    if constexpr (LANE_LOCAL) asm volatile("" : "+v"(loff));
     const uint8_t* src = a.blob + st.src_off;
     const int nchunk = st.bytes >> 10;
     for (int c = wave; c < nchunk; c += kWavesPerBlock) {
-        __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(src + (c << 10) + lane * 16),
+        const uint8_t* from = LANE_LOCAL ? src + (c << 10) + loff : src + (c << 10) + lane * 16;
+        __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(from),
                                          (__attribute__((address_space(3))) void*)(dst + (c << 10)),
                                          16, 0, 0);
     }
 }
 
+template <bool LANE_LOCAL = false>
 __device__ __forceinline__ void stager_start(Stager& sg, const ChainArgs& a) {
     sg.idx = -1;
     sg.cur = -1;
-    if (sg.n > 0) dma_stage(a, cload(sg.sched, 0), sg.base);
+    if (sg.n > 0) dma_stage<LANE_LOCAL>(a, cload(sg.sched, 0), sg.base);
 }
 
 // Make stage `s` resident (uniform across the workgroup).
+template <bool LANE_LOCAL = false>
 __device__ __forceinline__ void ensure_stage(int s, Stager& sg, const ChainArgs& a) {
     if (s == sg.cur) return;
 #ifdef DF_EXP_NOSYNC  // diagnostic build only: no stage switches (results are wrong)
@@ -170,7 +180,7 @@ __device__ __forceinline__ void ensure_stage(int s, Stager& sg, const ChainArgs&
         sg.n = 0;  // schedule abandoned: every further switch copies synchronously
         return;
     }
-    if (nidx + 1 < sg.n) dma_stage(a, cload(sg.sched, nidx + 1), sg.base + (((nidx + 1) & 1) ? sg.bytes : 0));
+    if (nidx + 1 < sg.n) dma_stage<LANE_LOCAL>(a, cload(sg.sched, nidx + 1), sg.base + (((nidx + 1) & 1) ? sg.bytes : 0));
 }
 
 constexpr int out_tiles(int HT) { return HT < 2 ? HT : 2; }

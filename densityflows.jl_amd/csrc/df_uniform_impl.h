@@ -574,6 +574,180 @@ __device__ __forceinline__ void dense_hidden_split(const uint8_t* wb, const f32x
     }
 }
 
+// ---- SPLIT variant, LDS reads ahead of their use (DF_SPLIT_PREFETCH) ----
+// The straight form above reads every fragment right before the MFMAs that take it, so
+// a wave stands in s_waitcnt lgkmcnt(0) for one LDS round trip per m-tile, per first-
+// Dense fragment and per output-weight vector: a third of its life
+// (profiles/prefetch_isa_waits.txt).  Here every read is requested one step ahead: the
+// step's own matrix (or fma) work runs between a request and its wait.  Arithmetic,
+// operand order and roundings are those of the straight form: bitwise the same outputs.
+//
+// The waits cannot be counted ones (lgkmcnt(n) leaving the newest n requests in flight):
+// while a stage DMA (global_load_lds) is outstanding, which is the whole net, the
+// compiler retires every LDS read with lgkmcnt(0).  So a step waits for its own reads
+// FIRST (lds_wait0, written out: the compiler adds no wait of its own after it) and only
+// then requests the next step's.  The order is pinned with scheduling barriers; left
+// alone the scheduler sinks the reads back to their uses, or spreads them until the
+// instance spills.
+#ifndef DF_SPLIT_PREFETCH
+#define DF_SPLIT_PREFETCH 1
+#endif
+
+__device__ __forceinline__ void sched_fence() { __builtin_amdgcn_sched_barrier(0); }
+
+// s_waitcnt lgkmcnt(0) alone (vmcnt 63, expcnt 7: the stage DMA is not waited for)
+__device__ __forceinline__ void lds_wait0() { __builtin_amdgcn_s_waitcnt(0xc07f); }
+
+// What one (chunk c, m-tile m) step of the hidden Dense reads: the three weight planes
+// and, in chunk 0, the m-tile's bias (the start of its accumulator chains).
+struct SplitStep {
+    bf16x8 w0, w1, w2;
+    f32x4 b;
+};
+
+// wl = the Dense's fragments + lane * 16, bl = its bias + 16 g; steps are contiguous
+// (step s = c·HT + m at s·3072).  A step past the Dense requests nothing.
+template <int HT, bool BIAS>
+__device__ __forceinline__ void split_step_request(const uint8_t* wl, const uint8_t* bl, int s, SplitStep& f) {
+    if (s >= (HT / 2) * HT) return;
+    const uint8_t* p = wl + s * 3072;
+    f.w0 = *reinterpret_cast<const bf16x8*>(p);
+    f.w1 = *reinterpret_cast<const bf16x8*>(p + 1024);
+    f.w2 = *reinterpret_cast<const bf16x8*>(p + 2048);
+    if (BIAS && s < HT) f.b = lds4(bl + (s << 6));
+}
+
+// dense_hidden_split with the (c, m) nest as one sequence of HT/2 × HT steps on two
+// fragment sets: a step retires its own fragments (requested before the previous step's
+// MFMAs), requests the next step's and issues its 6·TT MFMAs.  The request of a chunk's
+// first step so precedes that chunk's activation split.  f0 = step 0, requested by the
+// caller.
+template <int HT, int TT, bool BIAS = true>
+__device__ __forceinline__ void dense_hidden_split_pf(const uint8_t* wb, int lane, const f32x4 (&in)[TT][HT],
+                                                      f32x4 (&out)[TT][HT], const SplitStep& f0) {
+    const int g = lane >> 4;
+    const uint8_t* bl = wb + (HT / 2) * HT * 3072 + (g << 4);
+    const uint8_t* wl = wb + lane * 16;
+    const short4v eye = neg_eye();
+    SplitStep f[2];
+    f[0] = f0;
+    bf16x8 x[TT][3];
+#pragma unroll
+    for (int s = 0; s < (HT / 2) * HT; ++s) {
+        const int c = s / HT, m = s % HT;
+        if (m == 0) {
+#pragma unroll
+            for (int t = 0; t < TT; ++t) split8_mrem(eye, in[t][2 * c], in[t][2 * c + 1], x[t][0], x[t][1], x[t][2]);
+        }
+        // the last step of a chunk is the register peak (its planes, all accumulators and
+        // the next chunk's f32 tiles): the next chunk's first request follows its MFMAs,
+        // where the planes are dead, and the activation split covers it
+        constexpr int NS = (HT / 2) * HT;
+        const bool late = (m == HT - 1) && (s + 1 < NS);
+        sched_fence();
+        lds_wait0();
+        if (!late) split_step_request<HT, BIAS>(wl, bl, s + 1, f[(s + 1) & 1]);
+        sched_fence();
+        const SplitStep& w = f[s & 1];
+#pragma unroll
+        for (int t = 0; t < TT; ++t) {  // small terms first
+            f32x4 a = c == 0 ? (BIAS ? w.b : f32x4{0.f, 0.f, 0.f, 0.f}) : out[t][m];
+            a = mfma_bf(w.w2, x[t][0], a);
+            a = mfma_bf(w.w1, x[t][1], a);
+            a = mfma_bf(w.w0, x[t][2], a);
+            a = mfma_bf(w.w1, x[t][0], a);
+            a = mfma_bf(w.w0, x[t][1], a);
+            out[t][m] = mfma_bf(w.w0, x[t][0], a);
+        }
+        if (late) {
+#pragma unroll
+            for (int t = 0; t < TT; ++t) asm volatile("" : "+v"(out[t][m]));  // the MFMAs stay above the request
+            sched_fence();
+            split_step_request<HT, BIAS>(wl, bl, s + 1, f[(s + 1) & 1]);
+        }
+    }
+}
+
+// dense_first_split on fragments w[HT] the caller requested ahead of the feature reads:
+// HT × TT MFMAs back to back.
+template <int HT, int TT>
+__device__ __forceinline__ void dense_first_split_pf(const bf16x8 (&w)[HT], const float (&xin)[TT][4],
+                                                     f32x4 (&acc)[TT][HT]) {
+    bf16x8 b[TT];
+    const __bf16 z = (__bf16)0.f;
+#pragma unroll
+    for (int t = 0; t < TT; t += 2) {  // tiles in pairs: one split of two values
+        bf16x2 h, m, l;
+        split2(xin[t][0], t + 1 < TT ? xin[t + 1][0] : 0.f, h, m, l);
+        b[t] = bf16x8{h[0], m[0], h[0], l[0], m[0], h[0], z, z};
+        if (t + 1 < TT) b[t + 1] = bf16x8{h[1], m[1], h[1], l[1], m[1], h[1], z, z};
+    }
+#pragma unroll
+    for (int m = 0; m < HT; ++m)
+#pragma unroll
+        for (int t = 0; t < TT; ++t) acc[t][m] = mfma_bf(w[m], b[t], f32x4{0.f, 0.f, 0.f, 0.f});
+}
+
+// The HT weight vectors of output oo (w3g = the output Dense + 16 g); nothing past NO.
+template <int HT, int NO>
+__device__ __forceinline__ void out_row_request(const uint8_t* w3g, int oo, f32x4 (&w)[HT]) {
+    if (oo >= NO) return;
+#pragma unroll
+    for (int kq = 0; kq < HT; ++kq) w[kq] = lds4(w3g + ((oo * 16 * HT + 16 * kq) << 2));
+}
+
+// out_valu_t on two sets of weight vectors: output 0's (w0, with the bias bo and the
+// coupling's slot word) were requested by the caller before the second relu; output
+// oo + 1's are requested ahead of output oo's 4·HT·TT fma, the coupling's old state
+// values (state[ro[t] + aslot] -> v) with output 1's.  fma order (oo, kq, r) and the swap
+// reduction as in out_valu_t.
+template <int HT, int TT, int NO>
+__device__ __forceinline__ void out_valu_t_pf(const uint8_t* w3g, const f32x4 (&w0)[HT], float bo,
+                                              const f32x4 (&h)[TT][HT], const float* state, const int (&ro)[TT],
+                                              const int& aslot, float (&v)[TT], float (&y)[TT]) {
+    static_assert(NO >= 1 && NO <= 4, "FAST tails: 1..4 outputs");
+    float p[TT][4];
+#pragma unroll
+    for (int t = 0; t < TT; ++t)
+#pragma unroll
+        for (int oo = 0; oo < 4; ++oo) p[t][oo] = 0.f;
+    f32x4 w[2][HT];
+#pragma unroll
+    for (int kq = 0; kq < HT; ++kq) w[0][kq] = w0[kq];
+#pragma unroll
+    for (int oo = 0; oo < NO; ++oo) {
+        sched_fence();
+        lds_wait0();
+        if (oo == 0) {
+#pragma unroll
+            for (int t = 0; t < TT; ++t) v[t] = state[ro[t] + aslot];
+        }
+        out_row_request<HT, NO>(w3g, oo + 1, w[(oo + 1) & 1]);
+        sched_fence();
+#pragma unroll
+        for (int kq = 0; kq < HT; ++kq)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int t = 0; t < TT; ++t) p[t][oo] = __builtin_fmaf(w[oo & 1][kq][r], h[t][kq][r], p[t][oo]);
+        // the fma are pure: without a use tied to the fences they sink below the next request
+#pragma unroll
+        for (int t = 0; t < TT; ++t) asm volatile("" : "+v"(p[t][oo]));
+    }
+#pragma unroll
+    for (int t = 0; t < TT; ++t) {
+        auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(p[t][0]), __float_as_uint(p[t][1]), false, false);
+        const float A = __uint_as_float(a[0]) + __uint_as_float(a[1]);  // rows: p0 g01, p1 g01, p0 g23, p1 g23
+        float Bv = 0.f;
+        if constexpr (NO > 2) {
+            auto b = __builtin_amdgcn_permlane16_swap(__float_as_uint(p[t][2]), __float_as_uint(p[t][3]), false, false);
+            Bv = __uint_as_float(b[0]) + __uint_as_float(b[1]);             // p2 g01, p3 g01, p2 g23, p3 g23
+        }
+        auto c = __builtin_amdgcn_permlane32_swap(__float_as_uint(A), __float_as_uint(Bv), false, false);
+        y[t] = (__uint_as_float(c[0]) + __uint_as_float(c[1])) + bo;      // group g: output g
+    }
+}
+
 // Evaluate net N for TT 16-sample tiles (state rows ro[t]) and apply its
 // coupling phase; sum[t] = Σ_k s_k for s phases (row order).
 template <int HT, int TT, bool OUTV, bool RELU, int PH, bool FAST = false, int NO = 0, bool SPLIT = false>
@@ -581,6 +755,57 @@ __device__ __forceinline__ void net_tiles(const uint8_t* buf, const UNet& N, con
                                           float* state, const int (&ro)[TT], float (&sum)[TT]) {
     const int lane = threadIdx.x & 63, g = lane >> 4;
     constexpr bool SPH = (PH == impl::PH_S_FWD || PH == impl::PH_S_BWD);
+#if DF_SPLIT_PREFETCH && !defined(DF_EXP_NOTAIL) && !defined(DF_DIAG_NOSPLIT)
+    if constexpr (SPLIT && FAST && HT >= 2 && OUTV && NO > 0) {
+        // the table word and the first-Dense fragments in one round trip, then the
+        // features (they need the word) with step 0 of the hidden Dense
+        // (every descriptor word of the body up front: a scalar load placed at its use
+        // is a round trip of its own in the middle of the tail)
+        // lane and g from an opaque copy of the thread id: derived here they die with the
+        // body; derived once per kernel every lane offset is a VGPR held across all bodies,
+        // which this instance (128 VGPRs) does not have
+        int tx = threadIdx.x;
+        asm volatile("" : "+v"(tx));
+        const int lane = tx & 63, g = lane >> 4;
+        const int off_out = N.off_out, af_tab = L.af_tab;
+        asm volatile("" ::"s"(off_out), "s"(af_tab));
+        const int slot = tab[L.feat_tab + g];
+        bf16x8 w0[HT];
+#pragma unroll
+        for (int m = 0; m < HT; ++m) w0[m] = *reinterpret_cast<const bf16x8*>(buf + N.off_w0 + lane * 16 + m * 1024);
+        sched_fence();
+        lds_wait0();
+        float xin[TT][4];
+#pragma unroll
+        for (int t = 0; t < TT; ++t) xin[t][0] = state[ro[t] + slot];
+        const uint8_t* wh = buf + N.off_h;
+        SplitStep f0;
+        split_step_request<HT, true>(wh + lane * 16, wh + (HT / 2) * HT * 3072 + (g << 4), 0, f0);
+        sched_fence();
+        f32x4 A[TT][HT], B[TT][HT];
+        dense_first_split_pf<HT, TT>(w0, xin, A);
+        bias_act<HT, TT, true>(buf, DF_ACT_RELU, A, false);
+        dense_hidden_split_pf<HT, TT>(wh, lane, A, B, f0);
+        // tail: the first output's weights, the bias and the slot word before the
+        // second relu
+        const uint8_t* w3g = buf + off_out + (g << 4);
+        sched_fence();
+        f32x4 wo[HT];
+        out_row_request<HT, NO>(w3g, 0, wo);
+        const float bo = reinterpret_cast<const float*>(buf + off_out)[NO * 16 * HT + (g < NO ? g : 0)];
+        const int aslot = tab[af_tab + (g < NO ? g : 0)];
+        sched_fence();
+        bias_act<HT, TT, true>(buf, DF_ACT_RELU, B, false);
+        float v[TT], y[TT];
+        out_valu_t_pf<HT, TT, NO>(w3g, wo, bo, B, state, ro, aslot, v, y);
+#pragma unroll
+        for (int t = 0; t < TT; ++t) {
+            if (g < NO) state[ro[t] + aslot] = couple1<PH>(v[t], y[t]);
+            sum[t] = SPH ? group_row_sum<NO>(y[t]) : 0.f;  // valid in lane group 0 (ldj_update)
+        }
+        return;
+    }
+#endif
     if constexpr (SPLIT && FAST && HT >= 2) {
         float xin[TT][4];
         const int slot = tab[L.feat_tab + g];
@@ -722,7 +947,8 @@ uniform_kernel(ChainArgs a) {
     sg.bytes = a.stage_bytes;
     sg.sched = FWD ? a.sched_fwd : a.sched_bwd;
     sg.n = FWD ? a.n_sched_fwd : a.n_sched_bwd;
-    impl::stager_start(sg, a);
+    constexpr bool kLaneLocalDma = SPLIT && DF_SPLIT_PREFETCH;  // df_chain_impl.h dma_stage
+    impl::stager_start<kLaneLocalDma>(sg, a);
 
     // Copy-in of the tables, the NormalizationLayer bounds (a.params, kept in LDS right
     // after the tables) and the state tile.  Fast form: every thread issues ALL its loads
@@ -851,13 +1077,26 @@ uniform_kernel(ChainArgs a) {
         const int kind = L.kind;
         const bool first_in_elem = FWD ? L.elem_start : L.elem_end;
         const bool last_in_elem = FWD ? L.elem_end : L.elem_start;
+        // SPLIT: the rarely run loops below (normalisation, snapshots) take their lane
+        // indices from an opaque copy of the thread id.  From the kernel's own they are
+        // loop-invariant, and their hoisted address arithmetic held some fifteen VGPRs
+        // across every net body of an instance that has 128.
+        int gl = g, jl = j, wavel = wave, row0l = row0;
+        if constexpr (kLaneLocalDma) {
+            if (kind == DF_LAYER_NORM || (!FWD && a.snap)) {
+                int tx = tid;
+                asm volatile("" : "+v"(tx));
+                gl = (tx & 63) >> 4, jl = tx & 15, wavel = tx >> 6;
+                row0l = ((wavel * nt) * 16 + jl) * stride;
+            }
+        }
         if (kind == DF_LAYER_NORM) {
             const float al = L.alpha, be = L.beta, delta = be - al;
             auto norm = [&](const auto* xmn) {
                 const auto* xmx = xmn + d;
                 for (int tt = 0; tt < nt; ++tt) {
-                    const int ro = row0 + tt * tstep;
-                    for (int i = g; i < d; i += 4) {
+                    const int ro = row0l + tt * tstep;
+                    for (int i = gl; i < d; i += 4) {
                         const float lo = xmn[i], hi = xmx[i], xd = hi - lo;
                         float v = state[ro + n + i];
                         if (FWD) v = ((xd * v - al * hi) + be * lo) / delta;
@@ -900,7 +1139,7 @@ uniform_kernel(ChainArgs a) {
                 }
             };
             auto run_net = [&](const UNet& N, auto ph_tag, bool sphase, float sign) {
-                impl::ensure_stage(N.stage, sg, a);
+                impl::ensure_stage<kLaneLocalDma>(N.stage, sg, a);
                 if constexpr (FAST && OUTV) {  // output count fixed per net: branch-free tails
                     switch (N.n_out) {
                         case 1: tiles_loop(N, ph_tag, std::integral_constant<int, 1>{}, sphase, sign); break;
@@ -969,9 +1208,9 @@ uniform_kernel(ChainArgs a) {
         if (!FWD && a.snap) {  // training: keep every layer's output for the reverse sweep
             float* dst = a.snap + (int64_t)li * a.batch * d;
             for (int tt = 0; tt < nt; ++tt) {
-                const int smp = (wave * nt + tt) * 16 + j;
+                const int smp = (wavel * nt + tt) * 16 + jl;
                 if (smp < nvalid)
-                    for (int i = g; i < d; i += 4) dst[(s0 + smp) * d + i] = state[row0 + tt * tstep + n + i];
+                    for (int i = gl; i < d; i += 4) dst[(s0 + smp) * d + i] = state[row0l + tt * tstep + n + i];
             }
         }
     }
