@@ -145,9 +145,9 @@ static bool same_bytes(const std::vector<T>& a, const std::vector<T>& b) {
 }
 
 template <typename T>
-static int refresh(const std::vector<T>& v, void* dst) {
+static int refresh(const std::vector<T>& v, const DevBuf& dst) {
     if (v.empty()) return DF_OK;
-    hipError_t e = hipMemcpy(dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+    hipError_t e = hipMemcpy(dst.get(), v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
     return e == hipSuccess ? DF_OK : hip_err(e, "hipMemcpy(weights)");
 }
 
@@ -170,14 +170,7 @@ int df_chain_destroy(df_chain* c) {
     if (!c) return DF_OK;
     if (c->n_trainers > 0) return set_err(DF_ERR_INVALID, "df_chain_destroy: destroy its df_train handles first");
     DeviceGuard gd(c->device);
-    void* ptrs[] = {c->d_layers, c->d_denses, c->d_chunks,  c->d_stages,  c->d_blob,  c->d_tables,
-                    c->d_params, c->d_bounds, c->d_partial, c->d_sched,   c->d_ulayers, c->d_wlayers,
-                    c->d_wstages, c->d_wblob, c->d_wbias,  c->d_wsched, c->d_sblob, c->d_sstages,
-                    c->d_ssched,  c->d_sulayers, c->d_wslayers, c->d_wsstages, c->d_wsblob, c->d_wssched,
-                    c->d_wstables, c->d_clk, c->d_theta_ws};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    delete c;
+    delete c;  // (its device buffers free themselves, on this device)
     return DF_OK;
 }
 
@@ -212,11 +205,11 @@ int df_chain_create(df_chain** out, const df_chain_desc* desc, int device) {
     const df::Plan& P = c->plan;
     std::vector<int32_t> sched_all(P.sched_fwd);
     sched_all.insert(sched_all.end(), P.sched_bwd.begin(), P.sched_bwd.end());
-    if ((rc = upload(P.layers, &c->d_layers)) != DF_OK || (rc = upload(P.denses, &c->d_denses)) != DF_OK ||
-        (rc = upload(P.chunks, &c->d_chunks)) != DF_OK || (rc = upload(P.stages, &c->d_stages)) != DF_OK ||
-        (rc = upload(P.blob, &c->d_blob)) != DF_OK || (rc = upload(P.tables, &c->d_tables)) != DF_OK ||
-        (rc = upload(P.params, &c->d_params)) != DF_OK || (rc = upload(sched_all, &c->d_sched)) != DF_OK ||
-        (rc = upload(P.ulayers, &c->d_ulayers)) != DF_OK) {
+    if ((rc = upload(P.layers, c->d_layers)) != DF_OK || (rc = upload(P.denses, c->d_denses)) != DF_OK ||
+        (rc = upload(P.chunks, c->d_chunks)) != DF_OK || (rc = upload(P.stages, c->d_stages)) != DF_OK ||
+        (rc = upload(P.blob, c->d_blob)) != DF_OK || (rc = upload(P.tables, c->d_tables)) != DF_OK ||
+        (rc = upload(P.params, c->d_params)) != DF_OK || (rc = upload(sched_all, c->d_sched)) != DF_OK ||
+        (rc = upload(P.ulayers, c->d_ulayers)) != DF_OK) {
         std::string m = g_err;
         df_chain_destroy(c);
         return set_err(rc, m);
@@ -224,9 +217,9 @@ int df_chain_create(df_chain** out, const df_chain_desc* desc, int device) {
     if (P.wide) {
         std::vector<int32_t> wsched(P.wsched_fwd);
         wsched.insert(wsched.end(), P.wsched_bwd.begin(), P.wsched_bwd.end());
-        if ((rc = upload(P.wlayers, &c->d_wlayers)) != DF_OK || (rc = upload(P.wstages, &c->d_wstages)) != DF_OK ||
-            (rc = upload(P.wblob, &c->d_wblob)) != DF_OK || (rc = upload(P.wbias, &c->d_wbias)) != DF_OK ||
-            (rc = upload(wsched, &c->d_wsched)) != DF_OK) {
+        if ((rc = upload(P.wlayers, c->d_wlayers)) != DF_OK || (rc = upload(P.wstages, c->d_wstages)) != DF_OK ||
+            (rc = upload(P.wblob, c->d_wblob)) != DF_OK || (rc = upload(P.wbias, c->d_wbias)) != DF_OK ||
+            (rc = upload(wsched, c->d_wsched)) != DF_OK) {
             std::string m = last_error();
             df_chain_destroy(c);
             return set_err(rc, m);
@@ -235,8 +228,8 @@ int df_chain_create(df_chain** out, const df_chain_desc* desc, int device) {
     if (P.split) {
         std::vector<int32_t> ssched(P.ssched_fwd);
         ssched.insert(ssched.end(), P.ssched_bwd.begin(), P.ssched_bwd.end());
-        if ((rc = upload(P.sulayers, &c->d_sulayers)) != DF_OK || (rc = upload(P.sstages, &c->d_sstages)) != DF_OK ||
-            (rc = upload(P.sblob, &c->d_sblob)) != DF_OK || (rc = upload(ssched, &c->d_ssched)) != DF_OK) {
+        if ((rc = upload(P.sulayers, c->d_sulayers)) != DF_OK || (rc = upload(P.sstages, c->d_sstages)) != DF_OK ||
+            (rc = upload(P.sblob, c->d_sblob)) != DF_OK || (rc = upload(ssched, c->d_ssched)) != DF_OK) {
             std::string m = last_error();
             df_chain_destroy(c);
             return set_err(rc, m);
@@ -245,15 +238,15 @@ int df_chain_create(df_chain** out, const df_chain_desc* desc, int device) {
     if (P.wsplit) {
         std::vector<int32_t> wssched(P.wssched_fwd);
         wssched.insert(wssched.end(), P.wssched_bwd.begin(), P.wssched_bwd.end());
-        if ((rc = upload(P.wslayers, &c->d_wslayers)) != DF_OK || (rc = upload(P.wsstages, &c->d_wsstages)) != DF_OK ||
-            (rc = upload(P.wsblob, &c->d_wsblob)) != DF_OK || (rc = upload(wssched, &c->d_wssched)) != DF_OK ||
-            (rc = upload(P.wstables, &c->d_wstables)) != DF_OK) {
+        if ((rc = upload(P.wslayers, c->d_wslayers)) != DF_OK || (rc = upload(P.wsstages, c->d_wsstages)) != DF_OK ||
+            (rc = upload(P.wsblob, c->d_wsblob)) != DF_OK || (rc = upload(wssched, c->d_wssched)) != DF_OK ||
+            (rc = upload(P.wstables, c->d_wstables)) != DF_OK) {
             std::string m = last_error();
             df_chain_destroy(c);
             return set_err(rc, m);
         }
     }
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->d_bounds), sizeof(float) * (2 * P.n + 4));
+    hipError_t e = c->d_bounds.alloc(sizeof(float) * (2 * P.n + 4));
     if (e != hipSuccess) {
         df_chain_destroy(c);
         return set_err(DF_ERR_NOMEM, "hipMalloc failed (θ bounds)");
@@ -426,7 +419,7 @@ int df_chain_set_theta_bounds(df_chain* c, const float* tmin, const float* tmax)
     std::memcpy(b.data(), tmin, sizeof(float) * n);
     std::memcpy(b.data() + n, tmax, sizeof(float) * n);
     DeviceGuard gd(c->device);
-    hipError_t e = hipMemcpy(c->d_bounds, b.data(), sizeof(float) * 2 * n, hipMemcpyHostToDevice);
+    hipError_t e = hipMemcpy(c->d_bounds.get(), b.data(), sizeof(float) * 2 * n, hipMemcpyHostToDevice);
     if (e != hipSuccess) return hip_err(e, "hipMemcpy(θ bounds)");
     c->h_bounds = b;
     c->has_bounds = true;
@@ -484,10 +477,8 @@ int run(df_chain* c, int mode, bool flow, const float* zin, const float* theta, 
     const int64_t grid = (batch + S - 1) / S;
     if (grid > 0x7fffffff) return set_err(DF_ERR_UNSUPPORTED, "batch too large for one launch");
     if (sum_out && grid > c->partial_cap) {
-        if (c->d_partial) (void)hipFree(c->d_partial);
-        c->d_partial = nullptr;
         c->partial_cap = 0;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->d_partial), sizeof(double) * grid);
+        hipError_t e = c->d_partial.alloc(sizeof(double) * grid);
         if (e != hipSuccess) return set_err(DF_ERR_NOMEM, "hipMalloc failed (NLL partials)");
         c->partial_cap = grid;
         c->partial_gen++;
@@ -500,45 +491,43 @@ int run(df_chain* c, int mode, bool flow, const float* zin, const float* theta, 
     if (hipStreamIsCapturing((hipStream_t)stream, &cap_status) != hipSuccess) cap_status = hipStreamCaptureStatusNone;
     const bool stamp = c->clk_on && cap_status == hipStreamCaptureStatusNone;
     if (stamp && grid > c->clk_cap) {  // stamp slots for this grid (zeroed: a new series)
-        if (c->d_clk) (void)hipFree(c->d_clk);
-        c->d_clk = nullptr;
         c->clk_cap = 0;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->d_clk), sizeof(uint64_t) * 2 * grid);
-        if (e == hipSuccess) e = hipMemsetAsync(c->d_clk, 0, sizeof(uint64_t) * 2 * grid, (hipStream_t)stream);
+        hipError_t e = c->d_clk.alloc(sizeof(uint64_t) * 2 * grid);
+        if (e == hipSuccess) e = hipMemsetAsync(c->d_clk.get(), 0, sizeof(uint64_t) * 2 * grid, (hipStream_t)stream);
         if (e != hipSuccess) return set_err(DF_ERR_NOMEM, "hipMalloc failed (clock stamps)");
         c->clk_cap = grid;
     }
 
     df::ChainArgs a{};
-    a.clk = stamp ? c->d_clk : nullptr;
+    a.clk = stamp ? c->d_clk.as<uint64_t>() : nullptr;
     a.zin = zin;
     a.theta = theta;
     a.xout = xout;
     a.ldj_out = ldj;
     a.lp_out = lp;
-    a.partial = sum_out ? c->d_partial : nullptr;
+    a.partial = sum_out ? c->d_partial.as<double>() : nullptr;
     a.batch = batch;
-    a.layers = static_cast<const df::DevLayer*>(c->d_layers);
-    a.denses = static_cast<const df::DevDense*>(c->d_denses);
-    a.chunks = static_cast<const df::DevChunk*>(c->d_chunks);
-    a.stages = static_cast<const df::DevStage*>(c->d_stages);
-    a.blob = static_cast<const uint8_t*>(c->d_blob);
-    a.tables = static_cast<const int32_t*>(c->d_tables);
-    a.params = static_cast<const float*>(c->d_params);
-    a.tmin = (flow && P.n > 0) ? c->d_bounds : nullptr;
-    a.tmax = (flow && P.n > 0) ? c->d_bounds + P.n : nullptr;
+    a.layers = c->d_layers.as<const df::DevLayer>();
+    a.denses = c->d_denses.as<const df::DevDense>();
+    a.chunks = c->d_chunks.as<const df::DevChunk>();
+    a.stages = c->d_stages.as<const df::DevStage>();
+    a.blob = c->d_blob.as<const uint8_t>();
+    a.tables = c->d_tables.as<const int32_t>();
+    a.params = c->d_params.as<const float>();
+    a.tmin = (flow && P.n > 0) ? c->d_bounds.as<const float>() : nullptr;
+    a.tmax = (flow && P.n > 0) ? c->d_bounds.as<const float>() + P.n : nullptr;
     a.d = P.d;
     a.n = P.n;
     a.stride = P.stride;
     a.tiles = tiles;
-    a.ulayers = static_cast<const df::ULayer*>(c->d_ulayers);
+    a.ulayers = c->d_ulayers.as<const df::ULayer>();
     a.n_layers = P.n_layers;
     a.tab_ints = (int)P.tables.size();
     a.tab_bytes = c->tab_bytes;
     a.n_par = (int)P.params.size();
     a.stage_bytes = c->stage_bytes;
     a.n_stage_bufs = c->n_stage_bufs;
-    a.sched_fwd = static_cast<const int32_t*>(c->d_sched);
+    a.sched_fwd = c->d_sched.as<const int32_t>();
     a.sched_bwd = a.sched_fwd + P.sched_fwd.size();
     a.n_sched_fwd = (int)P.sched_fwd.size();
     a.n_sched_bwd = (int)P.sched_bwd.size();
@@ -553,23 +542,23 @@ int run(df_chain* c, int mode, bool flow, const float* zin, const float* theta, 
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipError_t e;
     if (wide) {
-        a.blob = static_cast<const uint8_t*>(c->d_wblob);
-        a.stages = static_cast<const df::DevStage*>(c->d_wstages);
-        a.sched_fwd = static_cast<const int32_t*>(c->d_wsched);
+        a.blob = c->d_wblob.as<const uint8_t>();
+        a.stages = c->d_wstages.as<const df::DevStage>();
+        a.sched_fwd = c->d_wsched.as<const int32_t>();
         a.sched_bwd = a.sched_fwd + P.wsched_fwd.size();
         a.n_sched_fwd = (int)P.wsched_fwd.size();
         a.n_sched_bwd = (int)P.wsched_bwd.size();
-        a.wlayers = static_cast<const df::WLayer*>(c->d_wlayers);
-        a.wbias = static_cast<const float*>(c->d_wbias);
+        a.wlayers = c->d_wlayers.as<const df::WLayer>();
+        a.wbias = c->d_wbias.as<const float>();
         if (use_wsplit(c)) {
-            a.blob = static_cast<const uint8_t*>(c->d_wsblob);
-            a.stages = static_cast<const df::DevStage*>(c->d_wsstages);
-            a.sched_fwd = static_cast<const int32_t*>(c->d_wssched);
+            a.blob = c->d_wsblob.as<const uint8_t>();
+            a.stages = c->d_wsstages.as<const df::DevStage>();
+            a.sched_fwd = c->d_wssched.as<const int32_t>();
             a.sched_bwd = a.sched_fwd + P.wssched_fwd.size();
             a.n_sched_fwd = (int)P.wssched_fwd.size();
             a.n_sched_bwd = (int)P.wssched_bwd.size();
-            a.wlayers = static_cast<const df::WLayer*>(c->d_wslayers);
-            a.tables = static_cast<const int32_t*>(c->d_wstables);
+            a.wlayers = c->d_wslayers.as<const df::WLayer>();
+            a.tables = c->d_wstables.as<const int32_t>();
             a.tab_ints = (int)P.wstables.size();
             a.tab_bytes = c->wstab_bytes;
             a.fsave = fsave;  // features instead of H0 (the split kernel only)
@@ -585,12 +574,12 @@ int run(df_chain* c, int mode, bool flow, const float* zin, const float* theta, 
         }
         e = df::launch_small(mode, a, c->small_sd[fi], (unsigned)grid, st, c->small_waves);
     } else if (split) {
-        a.blob = static_cast<const uint8_t*>(c->d_sblob);
-        a.stages = static_cast<const df::DevStage*>(c->d_sstages);
-        a.ulayers = static_cast<const df::ULayer*>(c->d_sulayers);
+        a.blob = c->d_sblob.as<const uint8_t>();
+        a.stages = c->d_sstages.as<const df::DevStage>();
+        a.ulayers = c->d_sulayers.as<const df::ULayer>();
         a.stage_bytes = c->sstage_bytes;
         a.n_stage_bufs = c->sn_stage_bufs;
-        a.sched_fwd = static_cast<const int32_t*>(c->d_ssched);
+        a.sched_fwd = c->d_ssched.as<const int32_t>();
         a.sched_bwd = a.sched_fwd + P.ssched_fwd.size();
         a.n_sched_fwd = (int)P.ssched_fwd.size();
         a.n_sched_bwd = (int)P.ssched_bwd.size();
@@ -601,7 +590,7 @@ int run(df_chain* c, int mode, bool flow, const float* zin, const float* theta, 
     }
     if (e != hipSuccess) return hip_err(e, "chain kernel launch");
     if (sum_out) {
-        e = df::launch_reduce_partials(c->d_partial, grid, sum_out, st);
+        e = df::launch_reduce_partials(c->d_partial.as<const double>(), grid, sum_out, st);
         if (e != hipSuccess) return hip_err(e, "reduce kernel launch");
     }
     return DF_OK;
@@ -668,9 +657,9 @@ int df_chain_clock_probe(df_chain* c, int on) {
     if (!c) return set_err(DF_ERR_INVALID, "null chain");
     DeviceGuard gd(c->device);
     if (!gd.ok) return set_err(DF_ERR_HIP, "hipSetDevice failed");
-    if (on && c->d_clk) {
+    if (on && c->d_clk.get()) {
         hipError_t e = hipDeviceSynchronize();
-        if (e == hipSuccess) e = hipMemset(c->d_clk, 0, sizeof(uint64_t) * 2 * c->clk_cap);
+        if (e == hipSuccess) e = hipMemset(c->d_clk.get(), 0, sizeof(uint64_t) * 2 * c->clk_cap);
         if (e != hipSuccess) return hip_err(e, "hipMemset(clock stamps)");
     }
     c->clk_on = on != 0;
@@ -681,12 +670,12 @@ int df_chain_clock_read(df_chain* c, double* ghz_median, double* ghz_mean, int64
     if (!c || !ghz_median || !ghz_mean || !n_slots) return set_err(DF_ERR_INVALID, "null pointer");
     *ghz_median = *ghz_mean = 0.0;
     *n_slots = 0;
-    if (!c->d_clk || c->clk_cap == 0) return DF_OK;
+    if (!c->d_clk.get() || c->clk_cap == 0) return DF_OK;
     DeviceGuard gd(c->device);
     if (!gd.ok) return set_err(DF_ERR_HIP, "hipSetDevice failed");
     std::vector<uint64_t> h((size_t)2 * c->clk_cap);
     hipError_t e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(h.data(), c->d_clk, h.size() * sizeof(uint64_t), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(h.data(), c->d_clk.get(), h.size() * sizeof(uint64_t), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return hip_err(e, "hipMemcpy(clock stamps)");
     std::vector<double> ghz;
     double st = 0.0, sr = 0.0;

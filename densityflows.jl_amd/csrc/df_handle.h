@@ -12,6 +12,44 @@
 #include "df_kernels.h"
 #include "df_plan.h"
 
+// Move-only owner of one hipMalloc allocation.  The destructor frees on the current
+// device: handles are deleted inside their DeviceGuard scope.
+class DevBuf {
+  public:
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            reset();
+            p_ = o.p_;
+            o.p_ = nullptr;
+        }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    // frees what it held, then allocates (empty again on failure)
+    hipError_t alloc(size_t bytes) {
+        reset();
+        const hipError_t e = hipMalloc(&p_, bytes);
+        if (e != hipSuccess) p_ = nullptr;
+        return e;
+    }
+    void reset() {
+        if (p_) (void)hipFree(p_);
+        p_ = nullptr;
+    }
+    void* get() const { return p_; }
+    template <typename T>
+    T* as() const {
+        return static_cast<T*>(p_);
+    }
+
+  private:
+    void* p_ = nullptr;
+};
+
 struct df_chain {
     df::Plan plan;
     int device = 0;
@@ -27,59 +65,62 @@ struct df_chain {
     // df_chain_set_weights / df_chain_set_theta_bounds
     df::SmallDesc small_sd[2] = {};
     bool small_sd_ok[2] = {false, false};
-    void* d_layers = nullptr;
-    void* d_denses = nullptr;
-    void* d_chunks = nullptr;
-    void* d_stages = nullptr;
-    void* d_blob = nullptr;
-    void* d_tables = nullptr;
-    void* d_params = nullptr;
-    float* d_bounds = nullptr;  // [θmin (n) | θmax (n)]
+    DevBuf d_layers;
+    DevBuf d_denses;
+    DevBuf d_chunks;
+    DevBuf d_stages;
+    DevBuf d_blob;
+    DevBuf d_tables;
+    DevBuf d_params;
+    DevBuf d_bounds;  // float [θmin (n) | θmax (n)]
     bool has_bounds = false;
     std::vector<float> h_bounds;  // host copy of d_bounds (the small-batch kernel's descriptor)
-    double* d_partial = nullptr;
+    DevBuf d_partial;  // double [partial_cap]
     int64_t partial_cap = 0;
     int64_t partial_gen = 0;  // bumped when d_partial is reallocated (captured train graphs hold it)
     int stage_bytes = 0;
     int n_stage_bufs = 1;
-    void* d_sched = nullptr;    // [fwd schedule | bwd schedule]
-    void* d_ulayers = nullptr;  // specialised-kernel descriptors
+    DevBuf d_sched;    // [fwd schedule | bwd schedule]
+    DevBuf d_ulayers;  // specialised-kernel descriptors
     int n_cu = 0;
     int occ[4][df::kMaxTilesPerWave + 1] = {};  // resident workgroups per CU, by mode and tiles
     int tab_bytes = 0;
     size_t lds = 0;
     int n_trainers = 0;         // live df_train handles bound to this chain
     // wide-net kernel (plan.wide): its own blob, stages, schedules, descriptors
-    void* d_wlayers = nullptr;
-    void* d_wstages = nullptr;
-    void* d_wblob = nullptr;
-    void* d_wbias = nullptr;
-    void* d_wsched = nullptr;
+    DevBuf d_wlayers;
+    DevBuf d_wstages;
+    DevBuf d_wblob;
+    DevBuf d_wbias;
+    DevBuf d_wsched;
     size_t wide_lds = 0;
     // SPLIT variant of the FAST kernel (plan.split): its own blob, stages, schedules, descriptors
-    void* d_sblob = nullptr;
-    void* d_sstages = nullptr;
-    void* d_ssched = nullptr;
-    void* d_sulayers = nullptr;
+    DevBuf d_sblob;
+    DevBuf d_sstages;
+    DevBuf d_ssched;
+    DevBuf d_sulayers;
     int sstage_bytes = 0;
     int sn_stage_bufs = 1;
     size_t slds = 0;
     int socc[4][df::kMaxTilesPerWave + 1] = {};
     // SPLIT variant of the wide kernel (plan.wsplit)
-    void* d_wslayers = nullptr;
-    void* d_wsstages = nullptr;
-    void* d_wsblob = nullptr;
-    void* d_wssched = nullptr;
-    void* d_wstables = nullptr;
+    DevBuf d_wslayers;
+    DevBuf d_wsstages;
+    DevBuf d_wsblob;
+    DevBuf d_wssched;
+    DevBuf d_wstables;
     int wstab_bytes = 0;
     size_t wslds = 0;
     // effective-clock stamps (df_chain_clock_probe): 2 × uint64 per workgroup slot
-    uint64_t* d_clk = nullptr;
+    DevBuf d_clk;
     int64_t clk_cap = 0;  // workgroup slots
     bool clk_on = false;
-    // θ broadcast workspace of df_flow_sample (NTuple θ)
+    // θ broadcast workspace of df_flow_sample (NTuple θ), which allocates and grows it itself
     float* d_theta_ws = nullptr;
     int64_t theta_ws_cap = 0;
+    ~df_chain() {
+        if (d_theta_ws) (void)hipFree(d_theta_ws);
+    }
 };
 
 // SPLIT launches unless the chain was created under DF_F32_EXACT=1 (df_chain::exact)
@@ -106,13 +147,13 @@ struct DeviceGuard {
 };
 
 template <typename T>
-int upload(const std::vector<T>& v, void** dst) {
+int upload(const std::vector<T>& v, DevBuf& dst) {
     size_t bytes = v.size() * sizeof(T);
     if (bytes == 0) bytes = 16;
-    hipError_t e = hipMalloc(dst, bytes);
+    hipError_t e = dst.alloc(bytes);
     if (e != hipSuccess) return set_err(DF_ERR_NOMEM, "hipMalloc failed for the chain plan");
     if (!v.empty()) {
-        e = hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+        e = hipMemcpy(dst.get(), v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
         if (e != hipSuccess) return hip_err(e, "hipMemcpy(plan)");
     }
     return DF_OK;

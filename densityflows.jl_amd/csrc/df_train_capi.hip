@@ -86,10 +86,35 @@ struct TrainGraph {
     uint64_t last_use = 0;
 };
 
+// One device-side regather of a packed blob from the flat parameters (launch_repack, or
+// launch_repack_split for bf16x3 plane blobs).  The blob belongs to the chain or the trainer;
+// n = 0: the chain has no such blob, nothing launches.
+struct RepackMap {
+    void* blob = nullptr;
+    DevBuf dst, src;
+    int64_t n = 0;
+    bool split = false;
+};
+
+// The batch-sized buffers: ensure_capacity replaces them all together.
+struct BatchBufs {
+    DevBuf d_snap, d_zbar, d_ebuf;
+    std::vector<DevBuf> d_lh, d_ld;  // H_k and δ_k buffers [cap][lwidth]
+    std::vector<DevBuf> d_lv;        // σ'(x_k) buffers [cap][lwidth] (nets with LNet::pre)
+    DevBuf d_lyp[2];                 // ȳ  [cap][lwidth], by net parity
+    DevBuf d_lbp[2];                 // δ of the last hidden Dense [cap][lwidth], by net parity
+    DevBuf d_lx;                     // gathered conditioner input [cap][lwidth]
+    // hidden activations kept by the inverse pass (generic kernel): the sweep then
+    // skips the forward recompute.  [(layer·2 + net)·lmax_h + k][B][lwidth]
+    DevBuf d_hsave;
+    // H0-free sweep (df_train::fmode): feature rows and the relu mask of H0
+    DevBuf d_fsave, d_hmask;
+};
+
 struct df_train {
     df_chain* c = nullptr;
     df_adam opt{};
-    float* d_bt = nullptr;            // device βᵗ of the next update (Adam), [β1ᵗ, β2ᵗ]
+    DevBuf d_bt;                      // device βᵗ of the next update (Adam), [β1ᵗ, β2ᵗ]
     int64_t cap_gen = 0;              // bumped when the batch-sized buffers are reallocated
     hipStream_t cap_stream = nullptr; // capture stream of df_train_step_graph
     std::vector<TrainGraph> graphs;
@@ -101,25 +126,16 @@ struct df_train {
     std::vector<SweepOp> ops;
     std::vector<uint8_t> tblob;
     std::vector<int32_t> tdst, tsrc;
-    float* d_params = nullptr;
-    float* d_m = nullptr;
-    float* d_v = nullptr;
-    float* d_grad = nullptr;
-    float* d_partial = nullptr;
-    void* d_tblob = nullptr;
-    void* d_pdst = nullptr;
-    void* d_psrc = nullptr;
-    void* d_tdst = nullptr;
-    void* d_tsrc = nullptr;
-    float* d_snap = nullptr;
-    float* d_zbar = nullptr;
-    float* d_ebuf = nullptr;
-    double* d_lpsum = nullptr;
+    DevBuf d_params, d_m, d_v, d_grad, d_partial, d_lpsum;  // float [P] (d_partial: [grid][P]); double Σ logpdf
+    DevBuf d_tblob;
+    // every packed blob's regather from d_params, in launch order (df_train_create_ex)
+    std::vector<RepackMap> maps;
+    BatchBufs bb;
     bool debug = false;               // df_train_set_debug: refuse updates on a non-finite loss
     int theta_input = DF_THETA_AUTO;  // df_train_set_theta_input
     const double* last_lp = nullptr;  // Σ logpdf written by the last df_train_gradient
     int64_t last_n = 0;               // ... and the n_total it was taken over
-    int64_t cap = 0;       // batch capacity of snap / zbar / ebuf
+    int64_t cap = 0;       // batch capacity of bb
     int grid = 0;          // workgroups of a full net launch (resident on the device)
     size_t lds_max = 0;
     // df_train_logpdf_grad (score_net_kernel), planned on the first call: one launch per
@@ -134,30 +150,14 @@ struct df_train {
     std::vector<int32_t> ldst, lsrc; // repack map (float index ← trainables index)
     std::vector<uint8_t> tsblob;     // SPLIT W1ᵀ planes of the fused path (GNet::st_src)
     std::vector<int32_t> tsdst, tssrc; // repack map (byte offset ← trainables index·4 + plane)
-    void* d_tsblob = nullptr;
-    void* d_tsdst = nullptr;
-    void* d_tssrc = nullptr;
     std::vector<uint8_t> lsblob;     // SPLIT planes of the layer-wise Wᵀ operands (LOp::sfrag)
     std::vector<int32_t> lsdst, lssrc; // repack map (byte offset ← trainables index·4 + plane)
-    void* d_lsblob = nullptr;
-    void* d_lsdst = nullptr;
-    void* d_lssrc = nullptr;
-    void* d_lblob = nullptr;
-    void* d_ldst = nullptr;
-    void* d_lsrc = nullptr;
+    DevBuf d_tsblob, d_lsblob, d_lblob;
     int lgrid = 0;                   // workgroups of the dW kernels (partial rows)
     int lwidth = 16;                 // widest activation row (floats)
     int lmax_h = 1;                  // activation buffers needed (hidden Denses + 1)
-    std::vector<float*> d_lh, d_ld; // H_k and δ_k buffers [cap][lwidth]
-    std::vector<float*> d_lv;       // σ'(x_k) buffers [cap][lwidth] (nets with LNet::pre)
     bool any_pre = false;
-    float* d_lyp[2] = {nullptr, nullptr};  // ȳ  [cap][lwidth], by net parity
-    float* d_lbp[2] = {nullptr, nullptr};  // δ of the last hidden Dense [cap][lwidth], by net parity
-    float* d_lx = nullptr;           // gathered conditioner input [cap][lwidth]
-    // hidden activations kept by the inverse pass (generic kernel): the sweep then
-    // skips the forward recompute.  [(layer·2 + net)·lmax_h + k][B][lwidth]
-    float* d_hsave = nullptr;
-    bool hsave_on = false;
+    bool hsave_on = false;           // bb.d_hsave is in use
     // H0-free sweep (round 5; wide SPLIT chains of relu hidden-256 nets, DF_SWEEP_H0FREE): the
     // inverse pass keeps each net's features vcat(θ, u)[axis_nn] ([layer·2 + net][B][32])
     // and H1 only (d_hsave with one slot per net); the split dW1 recomputes H0 from the
@@ -165,48 +165,46 @@ struct df_train {
     bool fmode = false;
     int sweep_req = DF_SWEEP_AUTO;   // df_train_create_ex: the requested form (df_sweep_form)
     bool separate = false;           // DF_SWEEP_SEPARATE: unmerged dW / front launches
-    float* d_fsave = nullptr;
-    uint32_t* d_hmask = nullptr;
-    // repack maps of the chain's wide-kernel blob and biases (plan.wide)
-    void* d_wdst = nullptr;
-    void* d_wsrc = nullptr;
-    void* d_wbdst = nullptr;
-    void* d_wbsrc = nullptr;
-    // repack maps of the chain's SPLIT blobs (plan.split, plan.wsplit)
-    void* d_sdst = nullptr;
-    void* d_ssrc = nullptr;
-    void* d_wsdst = nullptr;
-    void* d_wssrc = nullptr;
 };
 
 namespace {
 
-void drop_graphs(df_train* t) {
+// the H0-free sweep is planned and its buffers fit (ensure_capacity)
+bool h0free(const df_train* t) { return t->fmode && t->hsave_on && t->bb.d_fsave.get(); }
+
+// The captured graphs and their stream (the device buffers free themselves with the handle).
+void free_all(df_train* t) {
     for (TrainGraph& g : t->graphs)
         if (g.exec) (void)hipGraphExecDestroy(g.exec);
     t->graphs.clear();
-}
-
-void free_all(df_train* t) {
-    drop_graphs(t);
     if (t->cap_stream) (void)hipStreamDestroy(t->cap_stream);
     t->cap_stream = nullptr;
-    if (t->d_bt) (void)hipFree(t->d_bt);
-    t->d_bt = nullptr;
-    void* ptrs[] = {t->d_params, t->d_m,    t->d_v,    t->d_grad, t->d_partial, t->d_tblob, t->d_pdst,
-                    t->d_psrc,   t->d_tdst, t->d_tsrc, t->d_snap, t->d_zbar,    t->d_ebuf,  t->d_lpsum,
-                    t->d_lblob,  t->d_ldst, t->d_lsrc, t->d_lyp[0], t->d_lyp[1], t->d_lbp[0], t->d_lbp[1], t->d_lx, t->d_hsave,
-                    t->d_wdst,   t->d_wsrc, t->d_wbdst, t->d_wbsrc, t->d_sdst, t->d_ssrc,
-                    t->d_wsdst, t->d_wssrc, t->d_lsblob, t->d_lsdst, t->d_lssrc,
-                    t->d_tsblob, t->d_tsdst, t->d_tssrc, t->d_fsave, t->d_hmask};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    for (float* p : t->d_lh)
-        if (p) (void)hipFree(p);
-    for (float* p : t->d_ld)
-        if (p) (void)hipFree(p);
-    for (float* p : t->d_lv)
-        if (p) (void)hipFree(p);
+}
+
+// Append the SPLIT planes [c][m][p][lane][8] of a Wᵀ (rows × kdim, mt row tiles, 32 k per
+// chunk; Wᵀ[i, k] = W[k, i] with W column-major, leading dimension ldw, at w_off of the
+// trainables) to blob, and (byte offset ← trainables index·4 + plane) to its repack map.
+// Returns the planes' byte offset in blob.
+int64_t pack_wt_planes(const Plan& P, int rows, int kdim, int mt, int chunks, int64_t w_off, int ldw,
+                       std::vector<uint8_t>& blob, std::vector<int32_t>& dst, std::vector<int32_t>& src) {
+    const int64_t base = (int64_t)blob.size();
+    blob.resize(blob.size() + (size_t)chunks * mt * 3072, 0);
+    for (int c = 0; c < chunks; ++c)
+        for (int m = 0; m < mt; ++m)
+            for (int p = 0; p < 3; ++p)
+                for (int lane = 0; lane < 64; ++lane)
+                    for (int e = 0; e < 8; ++e) {
+                        const int i = 16 * m + (lane & 15), g = lane >> 4;
+                        const int k = 32 * c + 16 * (e >> 2) + 4 * g + (e & 3);
+                        if (i >= rows || k >= kdim) continue;
+                        const int64_t from = w_off + k + (int64_t)ldw * i;
+                        const int64_t at = base + ((((int64_t)c * mt + m) * 3 + p) * 64 + lane) * 16 + 2 * e;
+                        const uint16_t h = bf16_split_plane(P.trainables[from], p);
+                        std::memcpy(&blob[at], &h, 2);
+                        dst.push_back((int32_t)at);
+                        src.push_back((int32_t)(from * 4 + p));
+                    }
+    return base;
 }
 
 // Pack A = W (transposed = false: rows = out, k = in) or Wᵀ (rows = in, k = out)
@@ -239,25 +237,8 @@ LOp pack_lop(df_train* t, const Plan& P, const LDense& D, bool transposed) {
     // SPLIT planes of a hidden-256 Wᵀ (the ldense_kernel SPLIT instances), and of a first
     // Dense's W0ᵀ over a 256-wide hidden layer (≤ 64 conditioner inputs: the x̄ product
     // of the SPLIT W1ᵀδ1 epilogue)
-    if (transposed && (op.mt == 16 || (op.mt <= 4 && op.nkq == 16)) && op.nkq % 2 == 0 && !t->c->exact) {
-        op.sfrag = (int64_t)t->lsblob.size();
-        t->lsblob.resize(t->lsblob.size() + (size_t)(op.nkq / 2) * op.mt * 3072, 0);
-        for (int c = 0; c < op.nkq / 2; ++c)
-            for (int m = 0; m < op.mt; ++m)
-                for (int p = 0; p < 3; ++p)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int e = 0; e < 8; ++e) {
-                            const int i = 16 * m + (lane & 15), g = lane >> 4;
-                            const int k = 32 * c + 16 * (e >> 2) + 4 * g + (e & 3);
-                            if (i >= rows || k >= kdim) continue;
-                            const int64_t src = D.w_off + k + (int64_t)D.out_dim * i;  // Wᵀ[i, k] = W[k, i]
-                            const int64_t at = op.sfrag + ((((int64_t)c * op.mt + m) * 3 + p) * 64 + lane) * 16 + 2 * e;
-                            const uint16_t h = bf16_split_plane(P.trainables[src], p);
-                            std::memcpy(&t->lsblob[at], &h, 2);
-                            t->lsdst.push_back((int32_t)at);
-                            t->lssrc.push_back((int32_t)(src * 4 + p));
-                        }
-    }
+    if (transposed && (op.mt == 16 || (op.mt <= 4 && op.nkq == 16)) && op.nkq % 2 == 0 && !t->c->exact)
+        op.sfrag = pack_wt_planes(P, rows, kdim, op.mt, op.nkq / 2, D.w_off, D.out_dim, t->lsblob, t->lsdst, t->lssrc);
     return op;
 }
 
@@ -421,26 +402,9 @@ int build_nets(df_train* t) {
                 g.su.off_out -= slo;
                 g.sfwd_src = P.sstages[s0.stage].src_off + slo;
                 g.sfwd_bytes = round16(shi - slo);
-                g.st_src = (int64_t)t->tsblob.size();
                 g.st_bytes = (ht / 2) * ht * 3072;
-                t->tsblob.resize(t->tsblob.size() + g.st_bytes, 0);
-                const int h = g.h_true;
-                for (int c = 0; c < ht / 2; ++c)
-                    for (int m = 0; m < ht; ++m)
-                        for (int p = 0; p < 3; ++p)
-                            for (int lane = 0; lane < 64; ++lane)
-                                for (int e = 0; e < 8; ++e) {
-                                    const int i = 16 * m + (lane & 15), gg = lane >> 4;
-                                    const int k = 32 * c + 16 * (e >> 2) + 4 * gg + (e & 3);
-                                    if (i >= h || k >= h) continue;
-                                    const int64_t src = D1->w_off + k + (int64_t)h * i;  // W1ᵀ[i, k] = W1[k, i]
-                                    const int64_t at =
-                                        g.st_src + ((((int64_t)c * ht + m) * 3 + p) * 64 + lane) * 16 + 2 * e;
-                                    const uint16_t hv = bf16_split_plane(P.trainables[src], p);
-                                    std::memcpy(&t->tsblob[at], &hv, 2);
-                                    t->tsdst.push_back((int32_t)at);
-                                    t->tssrc.push_back((int32_t)(src * 4 + p));
-                                }
+                g.st_src = pack_wt_planes(P, g.h_true, g.h_true, ht, ht / 2, D1->w_off, g.h_true, t->tsblob, t->tsdst,
+                                          t->tssrc);
             }
             t->nets.push_back(g);
             t->net_nh.push_back(u0.nh);
@@ -480,38 +444,20 @@ int ensure_capacity(df_train* t, int64_t batch) {
     if (batch <= t->cap) return DF_OK;
     t->cap_gen++;  // captured train steps name the old buffers
     const Plan& P = t->c->plan;
-    for (float** p : {&t->d_snap, &t->d_zbar, &t->d_ebuf})
-        if (*p) {
-            (void)hipFree(*p);
-            *p = nullptr;
-        }
+    t->bb = BatchBufs{};  // every old buffer goes before the new ones are sized (hipMemGetInfo below)
+    BatchBufs& bb = t->bb;
     t->cap = 0;
     const int64_t cap = std::max<int64_t>(batch, 1024);
-    for (float** p : {&t->d_lyp[0], &t->d_lyp[1], &t->d_lbp[0], &t->d_lbp[1], &t->d_lx, &t->d_hsave, &t->d_fsave})
-        if (*p) {
-            (void)hipFree(*p);
-            *p = nullptr;
-        }
-    if (t->d_hmask) (void)hipFree(t->d_hmask);
-    t->d_hmask = nullptr;
-    for (auto* v : {&t->d_lh, &t->d_ld, &t->d_lv}) {
-        for (float* p : *v)
-            if (p) (void)hipFree(p);
-        v->clear();
-    }
     const int ew = t->layerwise ? 32 : 4;  // exp(-s) row width
-    if (hipMalloc(reinterpret_cast<void**>(&t->d_snap), sizeof(float) * P.n_layers * cap * P.d) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&t->d_zbar), sizeof(float) * cap * P.d) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&t->d_ebuf), sizeof(float) * cap * ew) != hipSuccess)
-        return set_err(DF_ERR_NOMEM, "hipMalloc failed (training activations)");
+    auto nomem = [] { return set_err(DF_ERR_NOMEM, "hipMalloc failed (training activations)"); };
+    if (bb.d_snap.alloc(sizeof(float) * P.n_layers * cap * P.d) != hipSuccess ||
+        bb.d_zbar.alloc(sizeof(float) * cap * P.d) != hipSuccess ||
+        bb.d_ebuf.alloc(sizeof(float) * cap * ew) != hipSuccess)
+        return nomem();
     if (t->layerwise) {
         const size_t row = sizeof(float) * (size_t)cap * t->lwidth;
-        if (hipMalloc(reinterpret_cast<void**>(&t->d_lyp[0]), row) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&t->d_lyp[1]), row) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&t->d_lbp[0]), row) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&t->d_lbp[1]), row) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&t->d_lx), row) != hipSuccess)
-            return set_err(DF_ERR_NOMEM, "hipMalloc failed (training activations)");
+        for (DevBuf* b : {&bb.d_lyp[0], &bb.d_lyp[1], &bb.d_lbp[0], &bb.d_lbp[1], &bb.d_lx})
+            if (b->alloc(row) != hipSuccess) return nomem();
         // keep the inverse pass's hidden activations when the chain runs on the generic
         // kernel and they fit (else the sweep recomputes them)
         t->hsave_on = false;
@@ -526,38 +472,27 @@ int ensure_capacity(df_train* t, int64_t batch) {
                 const size_t fbytes = fm ? sizeof(float) * (size_t)cap * 32 * P.n_layers * 2 : 0;
                 const size_t mbytes = fm ? (size_t)(cap + 31) / 32 * 1024 : 0;
                 if (!info || hbytes + fbytes + mbytes >= free_b / 2) return false;
-                if (hipMalloc(reinterpret_cast<void**>(&t->d_hsave), hbytes) == hipSuccess &&
-                    (!fm || (hipMalloc(reinterpret_cast<void**>(&t->d_fsave), fbytes) == hipSuccess &&
-                             hipMalloc(reinterpret_cast<void**>(&t->d_hmask), mbytes) == hipSuccess)))
-                    return true;
-                for (float** p : {&t->d_hsave, &t->d_fsave})
-                    if (*p) {
-                        (void)hipFree(*p);
-                        *p = nullptr;
-                    }
-                if (t->d_hmask) (void)hipFree(t->d_hmask);
-                t->d_hmask = nullptr;
-                return false;
+                DevBuf h, f, m;  // (all three or none)
+                if (h.alloc(hbytes) != hipSuccess ||
+                    (fm && (f.alloc(fbytes) != hipSuccess || m.alloc(mbytes) != hipSuccess)))
+                    return false;
+                bb.d_hsave = std::move(h);
+                bb.d_fsave = std::move(f);
+                bb.d_hmask = std::move(m);
+                return true;
             };
             if (t->fmode && !try_keep(true)) t->fmode = false;  // sized for H0 and H1 below
             if (t->fmode || try_keep(false)) t->hsave_on = true;
             (void)hipGetLastError();
         }
         for (int k = 0; k <= t->lmax_h; ++k) {
-            float *h = nullptr, *dl = nullptr;
-            if (hipMalloc(reinterpret_cast<void**>(&h), row) != hipSuccess ||
-                hipMalloc(reinterpret_cast<void**>(&dl), row) != hipSuccess) {
-                if (h) (void)hipFree(h);
-                return set_err(DF_ERR_NOMEM, "hipMalloc failed (training activations)");
-            }
-            t->d_lh.push_back(h);
-            t->d_ld.push_back(dl);
-            if (t->any_pre && k < t->lmax_h) {
-                float* dv = nullptr;
-                if (hipMalloc(reinterpret_cast<void**>(&dv), row) != hipSuccess)
-                    return set_err(DF_ERR_NOMEM, "hipMalloc failed (training activations)");
-                t->d_lv.push_back(dv);
-            }
+            DevBuf h, dl, dv;
+            const bool pre = t->any_pre && k < t->lmax_h;
+            if (h.alloc(row) != hipSuccess || dl.alloc(row) != hipSuccess || (pre && dv.alloc(row) != hipSuccess))
+                return nomem();
+            bb.d_lh.push_back(std::move(h));
+            bb.d_ld.push_back(std::move(dl));
+            if (pre) bb.d_lv.push_back(std::move(dv));
         }
     }
     t->cap = cap;
@@ -565,123 +500,194 @@ int ensure_capacity(df_train* t, int64_t batch) {
 }
 
 int repack(df_train* t, hipStream_t st) {
-    df_chain* c = t->c;
-    const Plan& P = c->plan;
-    hipError_t e = launch_repack(static_cast<float*>(c->d_blob), static_cast<const int32_t*>(t->d_pdst),
-                                 static_cast<const int32_t*>(t->d_psrc), (int64_t)P.pack_dst.size(), t->d_params, st);
-    if (e == hipSuccess && !t->tdst.empty())
-        e = launch_repack(static_cast<float*>(t->d_tblob), static_cast<const int32_t*>(t->d_tdst),
-                          static_cast<const int32_t*>(t->d_tsrc), (int64_t)t->tdst.size(), t->d_params, st);
-    if (e == hipSuccess && P.wide) {
-        e = launch_repack(static_cast<float*>(c->d_wblob), static_cast<const int32_t*>(t->d_wdst),
-                          static_cast<const int32_t*>(t->d_wsrc), (int64_t)P.wpack_dst.size(), t->d_params, st);
-        if (e == hipSuccess)
-            e = launch_repack(static_cast<float*>(c->d_wbias), static_cast<const int32_t*>(t->d_wbdst),
-                              static_cast<const int32_t*>(t->d_wbsrc), (int64_t)P.wbias_dst.size(), t->d_params, st);
+    const float* params = t->d_params.as<const float>();
+    for (const RepackMap& m : t->maps) {
+        const int32_t *dst = m.dst.as<const int32_t>(), *src = m.src.as<const int32_t>();
+        const hipError_t e = m.split ? launch_repack_split(static_cast<uint8_t*>(m.blob), dst, src, m.n, params, st)
+                                     : launch_repack(static_cast<float*>(m.blob), dst, src, m.n, params, st);
+        if (e != hipSuccess) return hip_err(e, "repack kernel launch");
     }
-    if (e == hipSuccess && P.split)
-        e = launch_repack_split(static_cast<uint8_t*>(c->d_sblob), static_cast<const int32_t*>(t->d_sdst),
-                                static_cast<const int32_t*>(t->d_ssrc), (int64_t)P.spack_dst.size(), t->d_params, st);
-    if (e == hipSuccess && P.wsplit)
-        e = launch_repack_split(static_cast<uint8_t*>(c->d_wsblob), static_cast<const int32_t*>(t->d_wsdst),
-                                static_cast<const int32_t*>(t->d_wssrc), (int64_t)P.wspack_dst.size(), t->d_params,
-                                st);
-    if (e == hipSuccess && !t->ldst.empty())
-        e = launch_repack(static_cast<float*>(t->d_lblob), static_cast<const int32_t*>(t->d_ldst),
-                          static_cast<const int32_t*>(t->d_lsrc), (int64_t)t->ldst.size(), t->d_params, st);
-    if (e == hipSuccess && !t->tsdst.empty())
-        e = launch_repack_split(static_cast<uint8_t*>(t->d_tsblob), static_cast<const int32_t*>(t->d_tsdst),
-                                static_cast<const int32_t*>(t->d_tssrc), (int64_t)t->tsdst.size(), t->d_params, st);
-    if (e == hipSuccess && !t->lsdst.empty())
-        e = launch_repack_split(static_cast<uint8_t*>(t->d_lsblob), static_cast<const int32_t*>(t->d_lsdst),
-                                static_cast<const int32_t*>(t->d_lssrc), (int64_t)t->lsdst.size(), t->d_params, st);
-    return e == hipSuccess ? DF_OK : hip_err(e, "repack kernel launch");
+    return DF_OK;
 }
 
-// Reverse sweep of the layer-wise path (chain order; see df_ltrain.h).
-int lsweep(df_train* t, const float* x, const float* theta, int64_t batch, float inv_n, bool flow, hipStream_t st) {
-    df_chain* c = t->c;
+// The per-layer arguments every sweep kernel takes: LDenseArgs, TrainArgs and ScoreArgs
+// name them alike.
+template <typename Args>
+void fill_layer_args(Args& a, const df_train* t, int layer, int phase, const float* x, const float* theta, bool flow,
+                     int64_t batch) {
+    const df_chain* c = t->c;
     const Plan& P = c->plan;
+    const DevLayer& L = P.layers[layer];
+    const float* snap = t->bb.d_snap.as<const float>();
+    const float* bounds = c->d_bounds.as<const float>();
+    const int32_t* tables = c->d_tables.as<const int32_t>();
     const int64_t bd = batch * P.d;
-    const int64_t ntiles = (batch + 15) / 16;
-    const unsigned dgrid =
-        (unsigned)std::max<int64_t>(1, std::min<int64_t>(c->n_cu, (ntiles + kWavesPerBlock * kLTiles - 1) /
-                                                                          (kWavesPerBlock * kLTiles)));
-    const int W = t->lwidth;
-    const uint8_t* lb = static_cast<const uint8_t*>(t->d_lblob);
-    const float* lbf = static_cast<const float*>(t->d_lblob);
-    const uint8_t* lsb = static_cast<const uint8_t*>(t->d_lsblob);
-    const bool lsplit = !c->exact;   // the chain's arithmetic, fixed at df_chain_create
-    auto sfrag_of = [&](const LOp& op, int in_kind, int epi) -> const uint8_t* {
+    a.u_in = (layer + 1 < P.n_layers) ? snap + (int64_t)(layer + 1) * bd : x;
+    a.u_out = snap + (int64_t)layer * bd;
+    a.theta = theta;
+    a.tmin = flow ? bounds : nullptr;
+    a.tmax = flow ? bounds + P.n : nullptr;
+    a.feat = tables + L.feat_tab;
+    a.af = tables + L.af_tab;
+    a.d = P.d;
+    a.n = P.n;
+    a.n_af = L.n_af;
+    a.kind = L.kind;
+    a.phase = phase;
+    a.batch = batch;
+}
+
+// The adjoint of a NormalizationLayer, element-wise on z̄.
+hipError_t norm_adjoint(const df_train* t, int layer, float* zbar, int64_t batch, hipStream_t st) {
+    const Plan& P = t->c->plan;
+    const DevLayer& L = P.layers[layer];
+    const float* xmn = t->c->d_params.as<const float>() + L.norm_off;
+    return launch_norm_adjoint(zbar, xmn, xmn + P.d, L.alpha, L.beta, P.d, batch, st);
+}
+
+// Dynamic LDS declared for the three kernel families of the layer-wise sweep
+// (df_train_create_ex), and the most any accepted shape asks of each:
+//   ldense      f32 fragments: two chunk buffers of <= kLChunkBytes (chunk_kq·mt·1024 <= 32 KiB),
+//               64 KiB; SPLIT planes: two chunks of mt·3072 B, mt = 16: 96 KiB.  The XBAR forms
+//               add the resident W0ᵀ and test the sum against the limit themselves (xbar_apart).
+//   couple_bwd  both fragment sets, 2·ht·mto·1024 with ht <= 16: 64 KiB at mto = 2; at mto = 1
+//               32 KiB + front_dwo_lds(16) = 51,200 B: 83,968 B.
+//   sweep       the larger of the dW staging (kLdwLdsMax, 80 KiB) and its front: 83,968 B.
+// So no accepted shape reaches the check in LSweep::launch.
+constexpr size_t kLdenseLdsLimit = 160 * 1024;
+constexpr size_t kCoupleBwdLdsLimit = 160 * 1024;
+constexpr size_t kSweepLdsLimit = 160 * 1024;
+
+// LDS of an ldense launch: the operand's chunk buffers, two when it spans several chunks.
+size_t ldense_lds_bytes(const LOp& op, bool split) {
+    if (split) return (size_t)(op.nkq / 2 > 1 ? 2 : 1) * op.mt * 3072;
+    const int nchunks = (op.nkq + op.chunk_kq - 1) / op.chunk_kq;
+    return (size_t)(nchunks > 1 ? 2 : 1) * std::min(op.nkq, op.chunk_kq) * op.mt * 1024;
+}
+
+// The couple_bwd front of one net: its arguments, instance and LDS.
+struct Front {
+    LDenseArgs a;
+    int ht, mto;
+    size_t lds;
+};
+
+// The dW products of one net, by how they launch.
+struct DwJobs {
+    LdwArgs h0{};                // fmode: the split dW1 that recomputes H0 and writes its relu
+    bool has_h0 = false;         //   mask, launched before the W1ᵀδ1 product that reads the mask
+    std::vector<LdwArgs> split;  // the other split 256×256 products: each its own launch, first
+    std::vector<LdwArgs> rest;   // merged into one launch with the next net's front, or one each
+};
+
+// What the steps of one layer-wise sweep share (lsweep).
+struct LSweep {
+    df_train* t;
+    df_chain* c;
+    const float* x;
+    const float* theta;
+    int64_t batch;
+    float inv_n;
+    bool flow;
+    hipStream_t st;
+    unsigned dgrid;           // workgroups of the Dense kernels
+    const uint8_t* lb;        // the layer-wise blob: fragments
+    const float* lbf;         //   ... and padded biases
+    const uint8_t* lsb;       // its SPLIT planes
+    bool lsplit;              // the chain's arithmetic, fixed at df_chain_create
+    bool fm;                  // H0-free sweep (struct df_train)
+    int par = 0;              // buffer parity of the current net
+    bool front_done = false;  // this net's couple_bwd ran in the previous merged launch
+    int rc = DF_OK;           // the first error: nothing launches after it
+
+    void fail(int code, const char* msg) {
+        if (rc == DF_OK) rc = set_err(code, msg);
+    }
+    // Every launch of the sweep goes through one of these two.
+    template <typename Launch>
+    void launch(const char* where, Launch&& go) {
+        if (rc != DF_OK) return;
+        const hipError_t e = go();
+        if (e != hipSuccess) rc = hip_err(e, where);
+    }
+    // ... with dynamic LDS: the request is held against what the kernel family declares
+    template <typename Launch>
+    void launch(const char* where, const char* family, size_t lds, size_t limit, Launch&& go) {
+        if (lds > limit)
+            fail(DF_ERR_UNSUPPORTED, (std::string("layer-wise training: a ") + family +
+                                      " launch needs more LDS than its kernels declare").c_str());
+        launch(where, go);
+    }
+    void ldense(int mt, int in_kind, int epi, const LDenseArgs& a, size_t lds) {
+        launch("layer-wise dense launch", "ldense", lds, kLdenseLdsLimit,
+               [&] { return launch_ldense(mt, in_kind, epi, a, dgrid, lds, st); });
+    }
+    void gather(const LDenseArgs& a, int rows) {
+        launch("layer-wise dense launch", [&] { return launch_gather_features(a, rows, st); });
+    }
+    void ldw(const LdwArgs& w, const char* where) {
+        launch(where, [&] { return launch_ldw(w, (unsigned)t->lgrid, st); });
+    }
+
+    bool keeps(const SweepOp& op) const { return t->hsave_on && !t->lnets[op.net].pre; }
+    static int net_slot(const SweepOp& op) { return 2 * op.layer + (op.phase == TR_PHASE_T ? 1 : 0); }
+    // fmode: the net's feature rows [B][32] (written by the inverse pass)
+    float* fbuf(const SweepOp& op) const { return t->bb.d_fsave.as<float>() + (int64_t)net_slot(op) * batch * 32; }
+    // whether the net's backward front is the fused couple_bwd kernel (kept activations,
+    // <= 32 outputs, hidden <= 256)
+    bool fused_front(const SweepOp& op) const {
+        const LNet& N = t->lnets[op.net];
+        const int nd = (int)N.dn.size();
+        return nd >= 2 && keeps(op) && N.dn[nd - 1].fwd.mt <= 2 && N.dn[0].bwd.mt <= 4;
+    }
+    // H_k of a net: kept by the inverse pass, or recomputed into the shared buffers
+    float* Hbuf(const SweepOp& op, int k) const {
+        float* hsave = t->bb.d_hsave.as<float>();
+        const int64_t W = t->lwidth;
+        if (fm) return k == 1 ? hsave + (int64_t)net_slot(op) * batch * W : nullptr;  // H1 only
+        return keeps(op) ? hsave + ((int64_t)net_slot(op) * t->lmax_h + k) * batch * W : t->bb.d_lh[k].as<float>();
+    }
+    // ȳ and the δ of the last hidden Dense alternate between two buffers from net to
+    // net: a merged launch writes net i+1's while net i's dW products read net i's
+    float* ybuf(int p) const { return t->bb.d_lyp[p].as<float>(); }
+    float* dbuf(const SweepOp& op, int k, int p) const {
+        return k == (int)t->lnets[op.net].dn.size() - 2 ? t->bb.d_lbp[p].as<float>() : t->bb.d_ld[k].as<float>();
+    }
+    const uint8_t* sfrag_of(const LOp& op, int in_kind, int epi) const {
         return (lsplit && op.sfrag >= 0 && ldense_split_supported(op.mt, in_kind, epi)) ? lsb + op.sfrag : nullptr;
-    };
-    hipError_t e = hipSuccess;
-    auto dense = [&](const LOp& op, int in_kind, int epi, LDenseArgs a) {
+    }
+    // σ' argument of Dense k's output: H_k, or the stored σ'(x_k)
+    void dact(const SweepOp& op, int k, LDenseArgs& a) const {
+        const LNet& N = t->lnets[op.net];
+        a.hprev = N.pre ? t->bb.d_lv[k].as<float>() : Hbuf(op, k);
+        a.dact = N.pre ? trn::kDactStored : N.dn[k].act;
+    }
+    LDenseArgs base_args(const SweepOp& op) const {
+        LDenseArgs b{};
+        fill_layer_args(b, t, op.layer, op.phase, x, theta, flow, batch);
+        b.n_in = t->lnets[op.net].dn[0].in_dim;
+        b.zbar = t->bb.d_zbar.as<float>();
+        b.ebuf = t->bb.d_ebuf.as<float>();
+        b.inv_n = inv_n;
+        b.ld_in = b.ld_out = b.ld_h = b.ld_x = t->lwidth;
+        return b;
+    }
+    // one Dense product on operand op
+    void dense(const LOp& op, int in_kind, int epi, LDenseArgs a) {
         a.wfrag = lb + op.frag;
         a.bias = (op.bias >= 0 && (epi == LEPI_ACT || epi == LEPI_COUPLE)) ? lbf + op.bias : nullptr;
         a.nkq = op.nkq;
         a.chunk_kq = op.chunk_kq;
         a.sfrag = sfrag_of(op, in_kind, epi);
-        const int nchunks = (op.nkq + op.chunk_kq - 1) / op.chunk_kq;
-        const size_t lds = a.sfrag ? (size_t)(op.nkq / 2 > 1 ? 2 : 1) * op.mt * 3072
-                                   : (size_t)(nchunks > 1 ? 2 : 1) * std::min(op.nkq, op.chunk_kq) * op.mt * 1024;
-        if (e == hipSuccess) e = launch_ldense(op.mt, in_kind, epi, a, dgrid, lds, st);
-    };
-    // Per net op: base arguments, and whether its backward front is the fused
-    // couple_bwd kernel (kept activations, <= 32 outputs, hidden <= 256).
-    const size_t nops = t->ops.size();
-    auto base_args = [&](const SweepOp& op) {
-        const DevLayer& L = P.layers[op.layer];
-        const LNet& N = t->lnets[op.net];
-        LDenseArgs b{};
-        b.theta = theta;
-        b.tmin = flow ? c->d_bounds : nullptr;
-        b.tmax = flow ? c->d_bounds + P.n : nullptr;
-        b.u_in = (op.layer + 1 < P.n_layers) ? t->d_snap + (int64_t)(op.layer + 1) * bd : x;
-        b.u_out = t->d_snap + (int64_t)op.layer * bd;
-        b.feat = static_cast<const int32_t*>(c->d_tables) + L.feat_tab;
-        b.af = static_cast<const int32_t*>(c->d_tables) + L.af_tab;
-        b.n_in = N.dn[0].in_dim;
-        b.zbar = t->d_zbar;
-        b.ebuf = t->d_ebuf;
-        b.n_af = L.n_af;
-        b.phase = op.phase;
-        b.kind = L.kind;
-        b.inv_n = inv_n;
-        b.batch = batch;
-        b.d = P.d;
-        b.n = P.n;
-        b.ld_in = b.ld_out = b.ld_h = b.ld_x = W;
-        return b;
-    };
-    const bool no_merge = t->separate;  // DF_SWEEP_SEPARATE
-    auto keeps = [&](const SweepOp& op) { return t->hsave_on && !t->lnets[op.net].pre; };
-    const bool fm = t->fmode && t->hsave_on && t->d_fsave;  // H0-free sweep (struct df_train)
-    auto net_slot = [&](const SweepOp& op) { return 2 * op.layer + (op.phase == TR_PHASE_T ? 1 : 0); };
-    // fmode: the net's feature rows [B][32] (written by the inverse pass)
-    auto fbuf = [&](const SweepOp& op) { return t->d_fsave + (int64_t)net_slot(op) * batch * 32; };
-    auto fused_front = [&](const SweepOp& op) {
-        const LNet& N = t->lnets[op.net];
-        const int nd = (int)N.dn.size();
-        return nd >= 2 && keeps(op) && N.dn[nd - 1].fwd.mt <= 2 && N.dn[0].bwd.mt <= 4;
-    };
-    // H_k of a net: kept by the inverse pass, or recomputed into the shared buffers
-    auto Hbuf = [&](const SweepOp& op, int k) -> float* {
-        if (fm) return k == 1 ? t->d_hsave + (int64_t)net_slot(op) * batch * W : nullptr;  // H1 only
-        return keeps(op) ? t->d_hsave + ((int64_t)net_slot(op) * t->lmax_h + k) * batch * W : t->d_lh[k];
-    };
-    // ȳ and the δ of the last hidden Dense alternate between two buffers from net to
-    // net: a merged launch writes net i+1's while net i's dW products read net i's
-    auto ybuf = [&](int par) { return t->d_lyp[par]; };
-    auto dbuf = [&](const SweepOp& op, int k, int par) -> float* {
-        return k == (int)t->lnets[op.net].dn.size() - 2 ? t->d_lbp[par] : t->d_ld[k];
-    };
+        ldense(op.mt, in_kind, epi, a, ldense_lds_bytes(op, a.sfrag != nullptr));
+    }
     // couple_bwd: output Dense + pullback → ȳ, then δ_last = (W_outᵀ ȳ) ⊙ σ'(H)
-    auto front_args = [&](const SweepOp& op, int par, LDenseArgs& a, int* ht, int* mto, size_t* lds) {
+    Front front(const SweepOp& op, int p) const {
         const LNet& N = t->lnets[op.net];
         const int nd = (int)N.dn.size();
         const LDense& DO = N.dn[nd - 1];
-        a = base_args(op);
+        Front f{base_args(op), DO.bwd.mt, DO.fwd.mt, (size_t)2 * DO.bwd.mt * DO.fwd.mt * 1024};
+        LDenseArgs& a = f.a;
         a.act = DO.act;
         a.in = Hbuf(op, nd - 2);
         a.wfrag = lb + DO.fwd.frag;
@@ -689,269 +695,280 @@ int lsweep(df_train* t, const float* x, const float* theta, int64_t batch, float
         a.nkq = DO.fwd.nkq;
         a.w2frag = lb + DO.bwd.frag;
         a.nkq2 = DO.bwd.nkq;
-        a.out = ybuf(par);
-        a.out2 = dbuf(op, nd - 2, par);
+        a.out = ybuf(p);
+        a.out2 = dbuf(op, nd - 2, p);
         a.dact = N.dn[nd - 2].act;
-        *ht = DO.bwd.mt;
-        *mto = DO.fwd.mt;
-        *lds = (size_t)2 * DO.bwd.mt * DO.fwd.mt * 1024;
         if (front_dwo(DO.fwd.mt)) {  // the output Dense's dW / db come from the front (partial rows: lgrid)
-            a.dwo_partial = t->d_partial;
+            a.dwo_partial = t->d_partial.as<float>();
             a.dwo_p_total = t->P;
             a.dwo_w_off = DO.w_off;
             a.dwo_b_off = DO.b_off;
             a.dwo_m_true = DO.out_dim;
             a.dwo_n_true = DO.in_dim;
-            *lds += front_dwo_lds(DO.bwd.mt);
+            f.lds += front_dwo_lds(DO.bwd.mt);
         }
-    };
-    // dW = δ · inᵀ, db = Σ δ of every Dense of a net (per-workgroup partials)
-    auto dw_args = [&](const SweepOp& op, int par, std::vector<LdwArgs>& out) -> int {
-        const LNet& N = t->lnets[op.net];
-        const int nd = (int)N.dn.size();
-        for (int k = 0; k < nd; ++k) {
-            const LDense& D = N.dn[k];
-            if (k + 1 == nd && fused_front(op) && front_dwo(D.fwd.mt)) continue;  // (the front's)
-            LdwArgs w{};
-            w.da = (k + 1 == nd) ? ybuf(par) : dbuf(op, k, par);
-            w.lda = W;
-            w.m_true = D.out_dim;
-            w.mta = D.fwd.mt;
-            w.xb = (k == 0) ? (fm ? fbuf(op) : t->d_lx) : Hbuf(op, k - 1);
-            w.ldb = (k == 0 && fm) ? 32 : W;
-            w.n_true = D.in_dim;
-            w.ntb = D.bwd.mt;
-            w.partial = t->d_partial;
-            w.p_total = t->P;
-            w.w_off = D.w_off;
-            w.b_off = D.b_off;
-            w.batch = batch;
-            if (!ldw_shape(w.mta, w.ntb, &w.wm, &w.bm, &w.bn)) return set_err(DF_ERR_UNSUPPORTED, "dW tiling");
-            // hidden-256 × hidden-256 dW on bf16x3 split products (ldw_split_body)
-            w.split = (lsplit && w.mta == 16 && w.ntb == 16 && w.bm == kLdwBM && w.bn == kLdwBN) ? 1 : 0;
-            if (fm && k == 1) {  // dW1 with H0 recomputed from the features (and its relu mask)
-                if (!w.split || nd != 3) return set_err(DF_ERR_INVALID, "internal: H0-free sweep without the split dW1");
-                const WLayer& WL = P.wslayers[op.layer];
-                const WNet& WN = op.phase == TR_PHASE_T ? WL.t : WL.s;
-                const DevStage& S0 = P.wsstages[WN.stage0];
-                w.xb = nullptr;
-                w.feat = fbuf(op);
-                w.w0s = static_cast<const uint8_t*>(c->d_wsblob) + S0.src_off;
-                w.b0 = static_cast<const float*>(c->d_wbias) + WN.b0;
-                w.hmask = t->d_hmask;
-            }
-            out.push_back(w);
-        }
-        return DF_OK;
-    };
+        return f;
+    }
+};
 
-    int par = 0;               // buffer parity of the current net
-    bool front_done = false;   // this net's couple_bwd ran in the previous merged launch
-    for (size_t oi = 0; oi < nops; ++oi) {
-        const SweepOp& op = t->ops[oi];
-        const DevLayer& L = P.layers[op.layer];
-        if (op.net < 0) {
-            const float* xmn = static_cast<const float*>(c->d_params) + L.norm_off;
-            e = launch_norm_adjoint(t->d_zbar, xmn, xmn + P.d, L.alpha, L.beta, P.d, batch, st);
-            if (e != hipSuccess) return hip_err(e, "norm adjoint launch");
-            front_done = false;
+// forward (recompute): H_k = σ(W_k · in + b_k), then the output Dense + coupling pullback → ȳ
+void recompute_forward(LSweep& s, const SweepOp& op, const LDenseArgs& b, bool fused) {
+    df_train* t = s.t;
+    const LNet& N = t->lnets[op.net];
+    const int nd = (int)N.dn.size();
+    const bool keep = s.keeps(op);
+    float* lx = t->bb.d_lx.as<float>();
+    for (int k = 0; k < nd - (fused ? 1 : 0); ++k) {
+        LDenseArgs a = b;
+        a.act = N.dn[k].act;
+        if (k + 1 < nd && keep) {
+            if (k == 0 && !s.fm) {  // (fmode: the inverse pass kept the features)
+                a.xsave = lx;
+                s.gather(a, 16 * N.dn[0].bwd.mt);
+            }
             continue;
         }
-        const LNet& N = t->lnets[op.net];
-        const int nd = (int)N.dn.size();
-        const LDenseArgs b = base_args(op);
-        const bool keep = keeps(op);
-        const bool fused = fused_front(op);
-        if (fm && !fused) return set_err(DF_ERR_INVALID, "internal: H0-free sweep without the fused front");
-        // σ' argument of Dense k's output: H_k, or the stored σ'(x_k)
-        auto DACT = [&](int k, LDenseArgs& a) {
-            a.hprev = N.pre ? t->d_lv[k] : Hbuf(op, k);
-            a.dact = N.pre ? trn::kDactStored : N.dn[k].act;
-        };
-        // forward (recompute): H_k = σ(W_k · in + b_k), then the output Dense + coupling pullback → ȳ
-        for (int k = 0; k < nd - (fused ? 1 : 0); ++k) {
-            LDenseArgs a = b;
-            a.act = N.dn[k].act;
-            if (k + 1 < nd && keep) {
-                if (k == 0 && !fm) {  // (fmode: the inverse pass kept the features)
-                    a.xsave = t->d_lx;
-                    e = e == hipSuccess ? launch_gather_features(a, 16 * N.dn[0].bwd.mt, st) : e;
-                }
-                continue;
+        if (k == 0) {
+            a.xsave = lx;
+            if (nd == 1) {  // a single-Dense conditioner: its input is the gathered features
+                s.gather(a, 16 * N.dn[0].bwd.mt);
+                a.in = lx;
             }
-            if (k == 0) {
-                a.xsave = t->d_lx;
-                if (nd == 1) {  // a single-Dense conditioner: its input is the gathered features
-                    e = e == hipSuccess ? launch_gather_features(a, 16 * N.dn[0].bwd.mt, st) : e;
-                    a.in = t->d_lx;
-                }
-            } else {
-                a.in = Hbuf(op, k - 1);
-            }
-            if (k + 1 < nd) {
-                a.out = Hbuf(op, k);
-                a.dsave = N.pre ? t->d_lv[k] : nullptr;
-                dense(N.dn[k].fwd, k == 0 ? LIN_GATHER : LIN_BUF, LEPI_ACT, a);
-            } else {
-                a.out = ybuf(par);
-                dense(N.dn[k].fwd, LIN_BUF, LEPI_COUPLE, a);
-            }
-        }
-        // dW products of this net (launched after the backward; fmode: the split dW1 first,
-        // it writes the H0 relu mask the W1ᵀδ1 epilogue reads)
-        std::vector<LdwArgs> jobs;
-        {
-            const int rc0 = dw_args(op, par, jobs);
-            if (rc0 != DF_OK) return rc0;
-        }
-        // backward: δ_{k-1} = (W_kᵀ δ_k) ⊙ σ'(H_{k-1}); x̄ = W0ᵀ δ_0 → z̄ (identity dims)
-        const float* gcur = ybuf(par);
-        if (fused) {
-            // output Dense + pullback + (W_outᵀ ȳ) ⊙ σ'(H) in one pass (unless the previous
-            // merged launch ran it); the last W_kᵀ product carries x̄ = W0ᵀ δ0 in its epilogue
-            if (!front_done) {
-                LDenseArgs a;
-                int ht = 0, mto = 0;
-                size_t lds = 0;
-                front_args(op, par, a, &ht, &mto, &lds);
-                // (a front that writes dW partial rows runs on every row's workgroup)
-                const unsigned fgrid = front_dwo(mto) ? (unsigned)t->lgrid : dgrid;
-                if (e == hipSuccess) e = launch_couple_bwd(ht, mto, a, fgrid, lds, st);
-            }
-            gcur = dbuf(op, nd - 2, par);
-            if (fm) {
-                for (auto it = jobs.begin(); it != jobs.end(); ++it)
-                    if (it->feat) {
-                        if (e == hipSuccess) e = launch_ldw(*it, (unsigned)t->lgrid, st);
-                        jobs.erase(it);
-                        break;
-                    }
-            }
-            bool xbar_apart = false;  // x̄ = W0ᵀδ0 as its own product (a wide first Dense)
-            for (int k = nd - 2; k >= 1; --k) {
-                LDenseArgs c2 = b;
-                c2.in = gcur;
-                DACT(k - 1, c2);
-                if (fm && k == 1) {  // σ'(H0) from the mask the split dW1 just wrote
-                    c2.hprev = nullptr;
-                    c2.hmask = t->d_hmask;
-                }
-                c2.out = dbuf(op, k - 1, par);
-                if (k == 1) {
-                    c2.w0t = lb + N.dn[0].bwd.frag;
-                    c2.w0t_mt = N.dn[0].bwd.mt;
-                    c2.w0t_nkq = N.dn[0].bwd.nkq;
-                    const LOp& lo = N.dn[k].bwd;
-                    const int nchunks = (lo.nkq + lo.chunk_kq - 1) / lo.chunk_kq;
-                    const int xepi = (fm && k == 1) ? LEPI_DACT_XBAR_MASK : LEPI_DACT_XBAR;
-                    c2.sfrag = sfrag_of(lo, LIN_BUF, xepi);
-                    if (fm && !c2.sfrag) return set_err(DF_ERR_INVALID, "internal: H0-free sweep without the split W1ᵀδ1");
-                    // x̄ on split products when the W1ᵀδ1 product is SPLIT and W0ᵀ has planes
-                    c2.w0s = (c2.sfrag && N.dn[0].bwd.sfrag >= 0 && c2.w0t_nkq <= 16) ? lsb + N.dn[0].bwd.sfrag
-                                                                                     : nullptr;
-                    const size_t wbytes = c2.sfrag ? (size_t)(lo.nkq / 2 > 1 ? 2 : 1) * lo.mt * 3072
-                                                   : (size_t)(nchunks > 1 ? 2 : 1) * std::min(lo.nkq, lo.chunk_kq) *
-                                                         lo.mt * 1024;
-                    auto w0_bytes = [&]() {
-                        return c2.w0s ? (size_t)(c2.w0t_nkq / 2) * c2.w0t_mt * 3072
-                                      : (size_t)c2.w0t_mt * c2.w0t_nkq * 1024;
-                    };
-                    // W0ᵀ stays resident beside the W1ᵀ chunk buffers: with more than 32
-                    // conditioner inputs its split planes (or even its f32 fragments, at 64
-                    // inputs) do not fit; then the f32 fragments, or x̄ = W0ᵀδ0 as its own
-                    // product after the δ0 kernel
-                    constexpr size_t kLdsMax = 160 * 1024;
-                    if (wbytes + w0_bytes() + 64 > kLdsMax) c2.w0s = nullptr;
-                    const size_t lds2 = wbytes + w0_bytes() + 64;  // + z̄ column table
-                    c2.wfrag = lb + lo.frag;
-                    c2.nkq = lo.nkq;
-                    c2.chunk_kq = lo.chunk_kq;
-                    if (lds2 <= kLdsMax) {
-                        if (e == hipSuccess) e = launch_ldense(lo.mt, LIN_BUF, xepi, c2, dgrid, lds2, st);
-                    } else {
-                        if (fm) return set_err(DF_ERR_INVALID, "internal: H0-free sweep with a wide first Dense");
-                        c2.w0t = nullptr;
-                        dense(lo, LIN_BUF, LEPI_DACT, c2);
-                        xbar_apart = true;
-                    }
-                } else {
-                    dense(N.dn[k].bwd, LIN_BUF, LEPI_DACT, c2);
-                }
-                gcur = dbuf(op, k - 1, par);
-            }
-            if (nd == 2 || xbar_apart) {
-                LDenseArgs c3 = b;
-                c3.in = gcur;
-                dense(N.dn[0].bwd, LIN_BUF, LEPI_XBAR, c3);
-            }
-        }
-        for (int k = nd - 1; k >= 1 && !fused; --k) {
-            LDenseArgs a = b;
-            a.in = gcur;
-            DACT(k - 1, a);
-            a.out = dbuf(op, k - 1, par);
-            dense(N.dn[k].bwd, LIN_BUF, LEPI_DACT, a);
-            gcur = dbuf(op, k - 1, par);
-        }
-        if (!fused) {
-            LDenseArgs a = b;
-            a.in = gcur;
-            dense(N.dn[0].bwd, LIN_BUF, LEPI_XBAR, a);
-        }
-        if (e != hipSuccess) return hip_err(e, "layer-wise dense launch");
-        // dW products of this net, merged with the next net's front when that net is the
-        // next op and runs the fused front (its front reads only z̄ after this net's
-        // W1ᵀδ1 kernel, the kept H, and writes the other parity's ȳ / δ_last)
-        front_done = false;
-        // the split 256×256 dW runs as its own launch (one wave per SIMD, ldw_split_kernel)
-        for (auto it = jobs.begin(); it != jobs.end();) {
-            if (!it->split) {
-                ++it;
-                continue;
-            }
-            e = launch_ldw(*it, (unsigned)t->lgrid, st);
-            if (e != hipSuccess) return hip_err(e, "split dW kernel launch");
-            it = jobs.erase(it);
-        }
-        if (!no_merge && jobs.size() <= 3) {
-            SweepJob j{};
-            // narrow (HBM-bound) products first, the hidden×hidden one last: even
-            // workgroups run them in this order, odd ones in reverse
-            std::stable_sort(jobs.begin(), jobs.end(), [](const LdwArgs& p, const LdwArgs& q) {
-                return ldw_staging_samples(p) > ldw_staging_samples(q);
-            });
-            j.nw = (int)jobs.size();
-            for (int k = 0; k < j.nw; ++k) {
-                j.w[k] = jobs[k];
-                j.ws[k] = ldw_staging_samples(jobs[k]);
-            }
-            int ht = 0, mto = 1;
-            size_t lds = ldw_lds_bytes();
-            if (oi + 1 < nops && t->ops[oi + 1].net >= 0 && fused_front(t->ops[oi + 1])) {
-                size_t flds = 0;
-                int fht = 0, fmto = 0;
-                LDenseArgs fa;
-                front_args(t->ops[oi + 1], par ^ 1, fa, &fht, &fmto, &flds);
-                if (sweep_supported(fht, fmto)) {
-                    j.front = fa;
-                    j.has_front = 1;
-                    ht = fht;
-                    mto = fmto;
-                    lds = std::max(lds, flds);
-                }
-            }
-            e = launch_sweep(ht, mto, j, (unsigned)t->lgrid, lds, st);
-            if (e != hipSuccess) return hip_err(e, "merged sweep launch");
-            front_done = j.has_front != 0;
         } else {
-            for (const LdwArgs& w : jobs) {
-                e = launch_ldw(w, (unsigned)t->lgrid, st);
-                if (e != hipSuccess) return hip_err(e, "dW kernel launch");
-            }
+            a.in = s.Hbuf(op, k - 1);
         }
-        par ^= 1;
+        if (k + 1 < nd) {
+            a.out = s.Hbuf(op, k);
+            a.dsave = N.pre ? t->bb.d_lv[k].as<float>() : nullptr;
+            s.dense(N.dn[k].fwd, k == 0 ? LIN_GATHER : LIN_BUF, LEPI_ACT, a);
+        } else {
+            a.out = s.ybuf(s.par);
+            s.dense(N.dn[k].fwd, LIN_BUF, LEPI_COUPLE, a);
+        }
     }
-    return DF_OK;
+}
+
+// dW = δ · inᵀ, db = Σ δ of every Dense of a net (per-workgroup partials), classified by
+// how they launch (DwJobs)
+void dw_jobs(LSweep& s, const SweepOp& op, bool fused, DwJobs& out) {
+    df_train* t = s.t;
+    const Plan& P = s.c->plan;
+    const LNet& N = t->lnets[op.net];
+    const int nd = (int)N.dn.size();
+    const int W = t->lwidth;
+    for (int k = 0; k < nd; ++k) {
+        const LDense& D = N.dn[k];
+        if (k + 1 == nd && fused && front_dwo(D.fwd.mt)) continue;  // (the front's)
+        LdwArgs w{};
+        w.da = (k + 1 == nd) ? s.ybuf(s.par) : s.dbuf(op, k, s.par);
+        w.lda = W;
+        w.m_true = D.out_dim;
+        w.mta = D.fwd.mt;
+        w.xb = (k == 0) ? (s.fm ? s.fbuf(op) : t->bb.d_lx.as<float>()) : s.Hbuf(op, k - 1);
+        w.ldb = (k == 0 && s.fm) ? 32 : W;
+        w.n_true = D.in_dim;
+        w.ntb = D.bwd.mt;
+        w.partial = t->d_partial.as<float>();
+        w.p_total = t->P;
+        w.w_off = D.w_off;
+        w.b_off = D.b_off;
+        w.batch = s.batch;
+        if (!ldw_shape(w.mta, w.ntb, &w.wm, &w.bm, &w.bn)) {
+            s.fail(DF_ERR_UNSUPPORTED, "dW tiling");
+            return;
+        }
+        // hidden-256 × hidden-256 dW on bf16x3 split products (ldw_split_body)
+        w.split = (s.lsplit && w.mta == 16 && w.ntb == 16 && w.bm == kLdwBM && w.bn == kLdwBN) ? 1 : 0;
+        if (s.fm && k == 1) {  // dW1 with H0 recomputed from the features (and its relu mask)
+            if (!w.split || nd != 3) {
+                s.fail(DF_ERR_INVALID, "internal: H0-free sweep without the split dW1");
+                return;
+            }
+            const WLayer& WL = P.wslayers[op.layer];
+            const WNet& WN = op.phase == TR_PHASE_T ? WL.t : WL.s;
+            const DevStage& S0 = P.wsstages[WN.stage0];
+            w.xb = nullptr;
+            w.feat = s.fbuf(op);
+            w.w0s = s.c->d_wsblob.as<const uint8_t>() + S0.src_off;
+            w.b0 = s.c->d_wbias.as<const float>() + WN.b0;
+            w.hmask = t->bb.d_hmask.as<uint32_t>();
+            out.h0 = w;
+            out.has_h0 = true;
+        } else if (w.split) {
+            out.split.push_back(w);
+        } else {
+            out.rest.push_back(w);
+        }
+    }
+}
+
+// δ0 = (W1ᵀ δ1) ⊙ σ'(H0) with x̄ = W0ᵀ δ0 in its epilogue.  Returns false when W0ᵀ does not
+// fit beside the W1ᵀ chunk buffers: δ0 alone ran, and x̄ is left to its own product.
+bool w1t_delta_xbar(LSweep& s, const LNet& N, LDenseArgs& a) {
+    const LOp &lo = N.dn[1].bwd, &w0 = N.dn[0].bwd;
+    a.w0t = s.lb + w0.frag;
+    a.w0t_mt = w0.mt;
+    a.w0t_nkq = w0.nkq;
+    const int xepi = s.fm ? LEPI_DACT_XBAR_MASK : LEPI_DACT_XBAR;
+    a.sfrag = s.sfrag_of(lo, LIN_BUF, xepi);
+    if (s.fm && !a.sfrag) {
+        s.fail(DF_ERR_INVALID, "internal: H0-free sweep without the split W1ᵀδ1");
+        return true;
+    }
+    // x̄ on split products when the W1ᵀδ1 product is SPLIT and W0ᵀ has planes
+    a.w0s = (a.sfrag && w0.sfrag >= 0 && a.w0t_nkq <= 16) ? s.lsb + w0.sfrag : nullptr;
+    const size_t wbytes = ldense_lds_bytes(lo, a.sfrag != nullptr);
+    auto w0_bytes = [&]() {
+        return a.w0s ? (size_t)(a.w0t_nkq / 2) * a.w0t_mt * 3072 : (size_t)a.w0t_mt * a.w0t_nkq * 1024;
+    };
+    // W0ᵀ stays resident beside the W1ᵀ chunk buffers: with more than 32
+    // conditioner inputs its split planes (or even its f32 fragments, at 64
+    // inputs) do not fit; then the f32 fragments, or x̄ = W0ᵀδ0 as its own
+    // product after the δ0 kernel
+    if (wbytes + w0_bytes() + 64 > kLdenseLdsLimit) a.w0s = nullptr;
+    const size_t lds = wbytes + w0_bytes() + 64;  // + z̄ column table
+    a.wfrag = s.lb + lo.frag;
+    a.nkq = lo.nkq;
+    a.chunk_kq = lo.chunk_kq;
+    if (lds <= kLdenseLdsLimit) {
+        s.ldense(lo.mt, LIN_BUF, xepi, a, lds);
+        return true;
+    }
+    if (s.fm) {
+        s.fail(DF_ERR_INVALID, "internal: H0-free sweep with a wide first Dense");
+        return true;
+    }
+    a.w0t = nullptr;
+    s.dense(lo, LIN_BUF, LEPI_DACT, a);
+    return false;
+}
+
+// backward: δ_{k-1} = (W_kᵀ δ_k) ⊙ σ'(H_{k-1}) down to δ_0, then x̄ = W0ᵀ δ_0 → z̄ (identity
+// dims).  Behind the fused front, couple_bwd gives ȳ and the δ of the last hidden Dense in one
+// pass over H (unless the previous merged launch ran it), and the W1ᵀ product carries x̄ in
+// its epilogue.
+void backward(LSweep& s, const SweepOp& op, const LDenseArgs& b, bool fused, const DwJobs& jobs) {
+    df_train* t = s.t;
+    const LNet& N = t->lnets[op.net];
+    const int nd = (int)N.dn.size();
+    if (fused && !s.front_done) {
+        const Front f = s.front(op, s.par);
+        // (a front that writes dW partial rows runs on every row's workgroup)
+        const unsigned fgrid = front_dwo(f.mto) ? (unsigned)t->lgrid : s.dgrid;
+        s.launch("layer-wise dense launch", "couple_bwd", f.lds, kCoupleBwdLdsLimit,
+                 [&] { return launch_couple_bwd(f.ht, f.mto, f.a, fgrid, f.lds, s.st); });
+    }
+    if (jobs.has_h0) s.ldw(jobs.h0, "layer-wise dense launch");
+    const float* gcur = fused ? s.dbuf(op, nd - 2, s.par) : s.ybuf(s.par);
+    bool xbar_done = false;  // x̄ came out of the W1ᵀ δ1 launch
+    for (int k = nd - (fused ? 2 : 1); k >= 1; --k) {
+        LDenseArgs a = b;
+        a.in = gcur;
+        s.dact(op, k - 1, a);
+        if (s.fm && k == 1) {  // σ'(H0) from the mask the split dW1 just wrote
+            a.hprev = nullptr;
+            a.hmask = t->bb.d_hmask.as<uint32_t>();
+        }
+        a.out = s.dbuf(op, k - 1, s.par);
+        if (fused && k == 1)
+            xbar_done = w1t_delta_xbar(s, N, a);
+        else
+            s.dense(N.dn[k].bwd, LIN_BUF, LEPI_DACT, a);
+        gcur = a.out;
+    }
+    if (!xbar_done) {
+        LDenseArgs a = b;
+        a.in = gcur;
+        s.dense(N.dn[0].bwd, LIN_BUF, LEPI_XBAR, a);
+    }
+}
+
+// The dW products of net op oi after its backward: the split 256×256 ones as their own
+// launches (one wave per SIMD, ldw_split_kernel), the rest merged with the next net's front
+// when that net is the next op and runs the fused front (its front reads only z̄ after this
+// net's W1ᵀδ1 kernel, the kept H, and writes the other parity's ȳ / δ_last)
+void weight_grads(LSweep& s, size_t oi, DwJobs& jobs) {
+    df_train* t = s.t;
+    s.front_done = false;
+    for (const LdwArgs& w : jobs.split) s.ldw(w, "split dW kernel launch");
+    std::vector<LdwArgs>& rest = jobs.rest;
+    if (t->separate || rest.size() > 3) {  // DF_SWEEP_SEPARATE
+        for (const LdwArgs& w : rest) s.ldw(w, "dW kernel launch");
+        return;
+    }
+    SweepJob j{};
+    // narrow (HBM-bound) products first, the hidden×hidden one last: even
+    // workgroups run them in this order, odd ones in reverse
+    std::stable_sort(rest.begin(), rest.end(), [](const LdwArgs& p, const LdwArgs& q) {
+        return ldw_staging_samples(p) > ldw_staging_samples(q);
+    });
+    j.nw = (int)rest.size();
+    for (int k = 0; k < j.nw; ++k) {
+        j.w[k] = rest[k];
+        j.ws[k] = ldw_staging_samples(rest[k]);
+    }
+    int ht = 0, mto = 1;
+    size_t lds = ldw_lds_bytes();
+    if (oi + 1 < t->ops.size() && t->ops[oi + 1].net >= 0 && s.fused_front(t->ops[oi + 1])) {
+        const Front f = s.front(t->ops[oi + 1], s.par ^ 1);
+        if (sweep_supported(f.ht, f.mto)) {
+            j.front = f.a;
+            j.has_front = 1;
+            ht = f.ht;
+            mto = f.mto;
+            lds = std::max(lds, f.lds);
+        }
+    }
+    s.launch("merged sweep launch", "sweep", lds, kSweepLdsLimit,
+             [&] { return launch_sweep(ht, mto, j, (unsigned)t->lgrid, lds, s.st); });
+    s.front_done = j.has_front != 0;
+}
+
+// Reverse sweep of the layer-wise path (chain order; see df_ltrain.h).
+int lsweep(df_train* t, const float* x, const float* theta, int64_t batch, float inv_n, bool flow, hipStream_t st) {
+    df_chain* c = t->c;
+    const int64_t ntiles = (batch + 15) / 16;
+    const unsigned dgrid =
+        (unsigned)std::max<int64_t>(1, std::min<int64_t>(c->n_cu, (ntiles + kWavesPerBlock * kLTiles - 1) /
+                                                                          (kWavesPerBlock * kLTiles)));
+    LSweep s{};
+    s.t = t;
+    s.c = c;
+    s.x = x;
+    s.theta = theta;
+    s.batch = batch;
+    s.inv_n = inv_n;
+    s.flow = flow;
+    s.st = st;
+    s.dgrid = dgrid;
+    s.lb = t->d_lblob.as<const uint8_t>();
+    s.lbf = t->d_lblob.as<const float>();
+    s.lsb = t->d_lsblob.as<const uint8_t>();
+    s.lsplit = !c->exact;
+    s.fm = h0free(t);
+    for (size_t oi = 0; oi < t->ops.size() && s.rc == DF_OK; ++oi) {
+        const SweepOp& op = t->ops[oi];
+        if (op.net < 0) {
+            s.launch("norm adjoint launch",
+                     [&] { return norm_adjoint(t, op.layer, t->bb.d_zbar.as<float>(), batch, st); });
+            s.front_done = false;
+            continue;
+        }
+        const bool fused = s.fused_front(op);
+        if (s.fm && !fused) {
+            s.fail(DF_ERR_INVALID, "internal: H0-free sweep without the fused front");
+            break;
+        }
+        const LDenseArgs b = s.base_args(op);
+        recompute_forward(s, op, b, fused);
+        // (built before the backward: fmode's split dW1 runs inside it)
+        DwJobs jobs;
+        dw_jobs(s, op, fused, jobs);
+        backward(s, op, b, fused, jobs);
+        weight_grads(s, oi, jobs);
+        s.par ^= 1;
+    }
+    return s.rc;
 }
 
 }  // namespace
@@ -1041,9 +1058,10 @@ int df_train_create_ex(df_train** out, df_chain* c, const df_adam* opt, int swee
     }
     t->grid = std::max(1, c->n_cu * occ);
     if (t->layerwise) {
-        e = set_ldense_lds_limit(160 * 1024);
-        if (e == hipSuccess) e = set_couple_bwd_lds_limit(64 * 1024);
-        if (e == hipSuccess) e = set_sweep_lds_limit(std::max<size_t>(ldw_lds_bytes(), 64 * 1024));
+        // (the limits LSweep::launch holds every request against; derivation at the constants)
+        e = set_ldense_lds_limit(kLdenseLdsLimit);
+        if (e == hipSuccess) e = set_couple_bwd_lds_limit(kCoupleBwdLdsLimit);
+        if (e == hipSuccess) e = set_sweep_lds_limit(kSweepLdsLimit);
         if (e != hipSuccess) {
             df_train_destroy(t);
             return hip_err(e, "hipFuncSetAttribute(layer-wise training)");
@@ -1062,44 +1080,68 @@ int df_train_create_ex(df_train** out, df_chain* c, const df_adam* opt, int swee
         }
     }
     const size_t pb = sizeof(float) * (size_t)std::max<int64_t>(t->P, 4);
-    if (hipMalloc(reinterpret_cast<void**>(&t->d_params), pb) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&t->d_m), pb) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&t->d_v), pb) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&t->d_grad), pb) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&t->d_partial), pb * t->grid) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&t->d_lpsum), sizeof(double)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&t->d_bt), 2 * sizeof(float)) != hipSuccess) {
+    if (t->d_params.alloc(pb) != hipSuccess || t->d_m.alloc(pb) != hipSuccess || t->d_v.alloc(pb) != hipSuccess ||
+        t->d_grad.alloc(pb) != hipSuccess || t->d_partial.alloc(pb * t->grid) != hipSuccess ||
+        t->d_lpsum.alloc(sizeof(double)) != hipSuccess || t->d_bt.alloc(2 * sizeof(float)) != hipSuccess) {
         df_train_destroy(t);
         return set_err(DF_ERR_NOMEM, "hipMalloc failed (training state)");
     }
     {  // Optimisers.setup: βᵗ = β for the first update
         const float bt[2] = {t->opt.beta1, t->opt.beta2};
-        if (hipMemcpy(t->d_bt, bt, sizeof(bt), hipMemcpyHostToDevice) != hipSuccess) {
+        if (hipMemcpy(t->d_bt.get(), bt, sizeof(bt), hipMemcpyHostToDevice) != hipSuccess) {
             df_train_destroy(t);
             return set_err(DF_ERR_HIP, "hipMemcpy(Adam state)");
         }
     }
-    if ((rc = upload(t->tblob, &t->d_tblob)) != DF_OK || (rc = upload(t->lblob, &t->d_lblob)) != DF_OK ||
-        (rc = upload(t->ldst, &t->d_ldst)) != DF_OK || (rc = upload(t->lsrc, &t->d_lsrc)) != DF_OK ||
-        (rc = upload(P.pack_dst, &t->d_pdst)) != DF_OK || (rc = upload(P.wpack_dst, &t->d_wdst)) != DF_OK ||
-        (rc = upload(P.wpack_src, &t->d_wsrc)) != DF_OK || (rc = upload(P.wbias_dst, &t->d_wbdst)) != DF_OK ||
-        (rc = upload(P.wbias_src, &t->d_wbsrc)) != DF_OK ||
-        (rc = upload(P.pack_src, &t->d_psrc)) != DF_OK || (rc = upload(t->tdst, &t->d_tdst)) != DF_OK ||
-        (rc = upload(t->tsrc, &t->d_tsrc)) != DF_OK || (rc = upload(P.spack_dst, &t->d_sdst)) != DF_OK ||
-        (rc = upload(P.spack_src, &t->d_ssrc)) != DF_OK || (rc = upload(P.wspack_dst, &t->d_wsdst)) != DF_OK ||
-        (rc = upload(P.wspack_src, &t->d_wssrc)) != DF_OK || (rc = upload(t->lsblob, &t->d_lsblob)) != DF_OK ||
-        (rc = upload(t->lsdst, &t->d_lsdst)) != DF_OK || (rc = upload(t->lssrc, &t->d_lssrc)) != DF_OK ||
-        (rc = upload(t->tsblob, &t->d_tsblob)) != DF_OK || (rc = upload(t->tsdst, &t->d_tsdst)) != DF_OK ||
-        (rc = upload(t->tssrc, &t->d_tssrc)) != DF_OK) {
+    // The trainer's blobs and every blob's repack map, the table in the order repack() launches.
+    // A map that is switched off keeps its entry and its (16-byte) index arrays with n = 0,
+    // which launches nothing, and the device allocations below keep the sequence they have
+    // always had: where these buffers land on the device moves a small-batch step by 0.1 %
+    // (profiles/train_host_refactor_ab.txt), so neither drop one nor reorder them.
+    enum { MP, MT, MW, MWB, MS, MWS, ML, MTS, MLS, kMaps };
+    struct MapSrc {
+        const std::vector<int32_t>*dst, *src;
+        bool on, split;
+    };
+    const MapSrc ms[kMaps] = {{&P.pack_dst, &P.pack_src, true, false},
+                              {&t->tdst, &t->tsrc, !t->tdst.empty(), false},
+                              {&P.wpack_dst, &P.wpack_src, P.wide != 0, false},
+                              {&P.wbias_dst, &P.wbias_src, P.wide != 0, false},
+                              {&P.spack_dst, &P.spack_src, P.split != 0, true},
+                              {&P.wspack_dst, &P.wspack_src, P.wsplit != 0, true},
+                              {&t->ldst, &t->lsrc, !t->ldst.empty(), false},
+                              {&t->tsdst, &t->tssrc, !t->tsdst.empty(), true},
+                              {&t->lsdst, &t->lssrc, !t->lsdst.empty(), true}};
+    t->maps.resize(kMaps);
+    auto dst = [&](int i) { return upload(*ms[i].dst, t->maps[i].dst); };
+    auto src = [&](int i) { return upload(*ms[i].src, t->maps[i].src); };
+    auto both = [&](int i) {
+        const int rc2 = dst(i);
+        return rc2 != DF_OK ? rc2 : src(i);
+    };
+    if ((rc = upload(t->tblob, t->d_tblob)) != DF_OK || (rc = upload(t->lblob, t->d_lblob)) != DF_OK ||
+        (rc = both(ML)) != DF_OK || (rc = dst(MP)) != DF_OK || (rc = both(MW)) != DF_OK ||
+        (rc = both(MWB)) != DF_OK || (rc = src(MP)) != DF_OK || (rc = both(MT)) != DF_OK ||
+        (rc = both(MS)) != DF_OK || (rc = both(MWS)) != DF_OK ||
+        (rc = upload(t->lsblob, t->d_lsblob)) != DF_OK || (rc = both(MLS)) != DF_OK ||
+        (rc = upload(t->tsblob, t->d_tsblob)) != DF_OK || (rc = both(MTS)) != DF_OK) {
         std::string m = last_error();
         df_train_destroy(t);
         return set_err(rc, m);
     }
-    if (t->P > 0 && (hipMemcpy(t->d_params, P.trainables.data(), sizeof(float) * t->P, hipMemcpyHostToDevice) !=
+    void* const blobs[kMaps] = {c->d_blob.get(),  t->d_tblob.get(), c->d_wblob.get(),  c->d_wbias.get(), c->d_sblob.get(),
+                                c->d_wsblob.get(), t->d_lblob.get(), t->d_tsblob.get(), t->d_lsblob.get()};
+    for (int i = 0; i < kMaps; ++i) {
+        RepackMap& m = t->maps[i];
+        m.blob = blobs[i];
+        m.n = ms[i].on ? (int64_t)ms[i].dst->size() : 0;
+        m.split = ms[i].split;
+    }
+    if (t->P > 0 && (hipMemcpy(t->d_params.get(), P.trainables.data(), sizeof(float) * t->P, hipMemcpyHostToDevice) !=
                          hipSuccess ||
-                     hipMemset(t->d_m, 0, sizeof(float) * t->P) != hipSuccess ||
-                     hipMemset(t->d_v, 0, sizeof(float) * t->P) != hipSuccess ||
-                     hipMemset(t->d_grad, 0, sizeof(float) * t->P) != hipSuccess)) {
+                     hipMemset(t->d_m.get(), 0, sizeof(float) * t->P) != hipSuccess ||
+                     hipMemset(t->d_v.get(), 0, sizeof(float) * t->P) != hipSuccess ||
+                     hipMemset(t->d_grad.get(), 0, sizeof(float) * t->P) != hipSuccess)) {
         df_train_destroy(t);
         return set_err(DF_ERR_HIP, "initialising the training state failed");
     }
@@ -1119,7 +1161,7 @@ int df_train_sweep(const df_train* t, int* form) {
     else if (t->cap == 0)  // no gradient yet: the form ensure_capacity will try first
         *form = t->fmode ? DF_SWEEP_H0FREE
                          : (t->c->plan.uniform || t->sweep_req == DF_SWEEP_RECOMPUTE) ? DF_SWEEP_RECOMPUTE : DF_SWEEP_KEPT;
-    else if (t->fmode && t->hsave_on && t->d_fsave) *form = DF_SWEEP_H0FREE;
+    else if (h0free(t)) *form = DF_SWEEP_H0FREE;
     else *form = t->hsave_on ? DF_SWEEP_KEPT : DF_SWEEP_RECOMPUTE;
     if (t->layerwise && t->separate) *form |= DF_SWEEP_SEPARATE;
     return DF_OK;
@@ -1127,7 +1169,7 @@ int df_train_sweep(const df_train* t, int* form) {
 
 int df_train_grad_ptr(df_train* t, float** grad_dev) {
     if (!t || !grad_dev) return set_err(DF_ERR_INVALID, "null pointer");
-    *grad_dev = t->d_grad;
+    *grad_dev = t->d_grad.as<float>();
     return DF_OK;
 }
 
@@ -1167,11 +1209,12 @@ int df_train_gradient(df_train* t, const float* x, const float* theta_raw, int64
     DeviceGuard gd(c->device);
     if (!gd.ok) return set_err(DF_ERR_HIP, "hipSetDevice failed");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    t->last_lp = logpdf_sum ? logpdf_sum : t->d_lpsum;
+    double* lp = logpdf_sum ? logpdf_sum : t->d_lpsum.as<double>();  // where this gradient writes Σ logpdf
+    t->last_lp = lp;
     t->last_n = n_total;
     if (batch == 0) {
-        hipError_t e = hipMemsetAsync(t->d_grad, 0, sizeof(float) * t->P, st);
-        if (e == hipSuccess) e = hipMemsetAsync(const_cast<double*>(t->last_lp), 0, sizeof(double), st);
+        hipError_t e = hipMemsetAsync(t->d_grad.get(), 0, sizeof(float) * t->P, st);
+        if (e == hipSuccess) e = hipMemsetAsync(lp, 0, sizeof(double), st);
         return e == hipSuccess ? DF_OK : hip_err(e, "hipMemsetAsync");
     }
     if (!x) return set_err(DF_ERR_INVALID, "null input array");
@@ -1182,64 +1225,52 @@ int df_train_gradient(df_train* t, const float* x, const float* theta_raw, int64
     const bool flow = tf == 1;
     int rc = ensure_capacity(t, batch);
     if (rc != DF_OK) return rc;
+    const BatchBufs& bb = t->bb;
+    float *snap = bb.d_snap.as<float>(), *zbar = bb.d_zbar.as<float>();
+    float *partial = t->d_partial.as<float>(), *grad = t->d_grad.as<float>();
 
     // 1. inverse pass keeping every layer's output (U[li] = snap[li], U[0] = z)
-    const bool fm = t->fmode && t->hsave_on && t->d_fsave;  // H0-free sweep (features + H1 kept)
-    rc = run(c, MODE_LOGPDF, flow, x, theta_raw, nullptr, nullptr, nullptr, logpdf_sum ? logpdf_sum : t->d_lpsum,
-             batch, stream, t->d_snap, t->hsave_on ? t->d_hsave : nullptr, t->lwidth, fm ? 1 : t->lmax_h,
-             fm ? t->d_fsave : nullptr);
+    const bool fm = h0free(t);  // H0-free sweep (features + H1 kept)
+    rc = run(c, MODE_LOGPDF, flow, x, theta_raw, nullptr, nullptr, nullptr, lp, batch,
+             stream, snap, t->hsave_on ? bb.d_hsave.as<float>() : nullptr, t->lwidth, fm ? 1 : t->lmax_h,
+             fm ? bb.d_fsave.as<float>() : nullptr);
     if (rc != DF_OK) return rc;
-    const int64_t bd = batch * P.d;
     // 2. z̄ = z / N
     const float inv_n = 1.f / (float)n_total;
-    hipError_t e = launch_scale(t->d_zbar, t->d_snap, inv_n, bd, st);
+    hipError_t e = launch_scale(zbar, snap, inv_n, batch * P.d, st);
     if (e != hipSuccess) return hip_err(e, "scale kernel launch");
     // 3. reverse sweep, chain order
     if (t->layerwise) {
         rc = lsweep(t, x, theta_raw, batch, inv_n, flow, st);
         if (rc != DF_OK) return rc;
-        e = launch_reduce_grads(t->d_partial, t->lgrid, t->P, t->d_grad, st);
+        e = launch_reduce_grads(partial, t->lgrid, t->P, grad, st);
         return e == hipSuccess ? DF_OK : hip_err(e, "gradient reduction launch");
     }
     const int64_t ntiles = (batch + 15) / 16;
     const int grid = (int)std::min<int64_t>(t->grid, (ntiles + kTrainWaves - 1) / kTrainWaves);
     for (const SweepOp& op : t->ops) {
-        const DevLayer& L = P.layers[op.layer];
         if (op.net < 0) {
-            const float* xmn = static_cast<const float*>(c->d_params) + L.norm_off;
-            e = launch_norm_adjoint(t->d_zbar, xmn, xmn + P.d, L.alpha, L.beta, P.d, batch, st);
+            e = norm_adjoint(t, op.layer, zbar, batch, st);
             if (e != hipSuccess) return hip_err(e, "norm adjoint launch");
             continue;
         }
         TrainArgs a{};
-        a.u_in = (op.layer + 1 < P.n_layers) ? t->d_snap + (int64_t)(op.layer + 1) * bd : x;
-        a.u_out = t->d_snap + (int64_t)op.layer * bd;
-        a.theta = theta_raw;
-        a.tmin = flow ? c->d_bounds : nullptr;
-        a.tmax = flow ? c->d_bounds + P.n : nullptr;
-        a.feat = static_cast<const int32_t*>(c->d_tables) + L.feat_tab;
-        a.af = static_cast<const int32_t*>(c->d_tables) + L.af_tab;
-        a.zbar = t->d_zbar;
-        a.ebuf = t->d_ebuf;
-        a.partial = t->d_partial;
-        a.blob = static_cast<const uint8_t*>(c->d_blob);
-        a.tblob = static_cast<const uint8_t*>(t->d_tblob);
-        a.sblob = static_cast<const uint8_t*>(c->d_sblob);
-        a.tsblob = static_cast<const uint8_t*>(t->d_tsblob);
-        a.batch = batch;
+        fill_layer_args(a, t, op.layer, op.phase, x, theta_raw, flow, batch);
+        a.zbar = zbar;
+        a.ebuf = bb.d_ebuf.as<float>();
+        a.partial = partial;
+        a.blob = c->d_blob.as<const uint8_t>();
+        a.tblob = t->d_tblob.as<const uint8_t>();
+        a.sblob = c->d_sblob.as<const uint8_t>();
+        a.tsblob = t->d_tsblob.as<const uint8_t>();
         a.p_total = t->P;
-        a.d = P.d;
-        a.n = P.n;
-        a.n_af = L.n_af;
-        a.kind = L.kind;
-        a.phase = op.phase;
         a.inv_n = inv_n;
         a.net = t->nets[op.net];
         e = launch_train_net(P.ht, t->net_nh[op.net], t->amode, a, (unsigned)grid, t->lds_max, st);
         if (e != hipSuccess) return hip_err(e, "train kernel launch");
     }
     // 4. fixed-order reduction of the workgroup partials
-    e = launch_reduce_grads(t->d_partial, grid, t->P, t->d_grad, st);
+    e = launch_reduce_grads(partial, grid, t->P, grad, st);
     return e == hipSuccess ? DF_OK : hip_err(e, "gradient reduction launch");
 }
 
@@ -1305,15 +1336,16 @@ int df_train_logpdf_grad(df_train* t, const float* x, const float* theta, float*
     }
     int rc = ensure_capacity(t, batch);
     if (rc != DF_OK) return rc;
+    float* snap = t->bb.d_snap.as<float>();
+    const float* bounds = c->d_bounds.as<const float>();
 
     // 1. inverse pass keeping every layer's output (U[li] = snap[li], U[0] = z); lp per sample
-    rc = run(c, MODE_LOGPDF, flow, x, theta, nullptr, nullptr, logpdf_out, nullptr, batch, stream, t->d_snap);
+    rc = run(c, MODE_LOGPDF, flow, x, theta, nullptr, nullptr, logpdf_out, nullptr, batch, stream, snap);
     if (rc != DF_OK) return rc;
-    const int64_t bd = batch * P.d;
     // 2. z̄ = ∂logpdf(MvNormal(0,I), z)/∂z = -z.  grad_x has z̄'s layout ([sample][d]): the
     //    sweep runs in it, and what is left after the last layer is ∂lp/∂x
-    float* zbar = grad_x ? grad_x : t->d_zbar;
-    hipError_t e = launch_scale(zbar, t->d_snap, -1.f, bd, st);
+    float* zbar = grad_x ? grad_x : t->bb.d_zbar.as<float>();
+    hipError_t e = launch_scale(zbar, snap, -1.f, batch * P.d, st);
     if (e != hipSuccess) return hip_err(e, "scale kernel launch");
     // θ̄ accumulates in grad_theta ([sample][n]) over the nets that read θ
     if (grad_theta) {
@@ -1324,32 +1356,18 @@ int df_train_logpdf_grad(df_train* t, const float* x, const float* theta, float*
     const int64_t ntiles = (batch + 15) / 16;
     const int grid = (int)std::min<int64_t>(t->score_grid, (ntiles + kScoreWaves - 1) / kScoreWaves);
     for (const ScoreOp& op : t->score_ops) {
-        const DevLayer& L = P.layers[op.layer];
         if (op.net < 0) {
-            const float* xmn = static_cast<const float*>(c->d_params) + L.norm_off;
-            e = launch_norm_adjoint(zbar, xmn, xmn + P.d, L.alpha, L.beta, P.d, batch, st);
+            e = norm_adjoint(t, op.layer, zbar, batch, st);
             if (e != hipSuccess) return hip_err(e, "norm adjoint launch");
             continue;
         }
         ScoreArgs a{};
-        a.u_in = (op.layer + 1 < P.n_layers) ? t->d_snap + (int64_t)(op.layer + 1) * bd : x;
-        a.u_out = t->d_snap + (int64_t)op.layer * bd;
-        a.theta = theta;
-        a.tmin = flow ? c->d_bounds : nullptr;
-        a.tmax = flow ? c->d_bounds + P.n : nullptr;
-        a.feat = static_cast<const int32_t*>(c->d_tables) + L.feat_tab;
-        a.af = static_cast<const int32_t*>(c->d_tables) + L.af_tab;
+        fill_layer_args(a, t, op.layer, op.phase, x, theta, flow, batch);
         a.zbar = zbar;
         a.thbar = grad_theta;
-        a.ebuf = t->d_ebuf;
-        a.blob = static_cast<const uint8_t*>(c->d_blob);
-        a.tblob = static_cast<const uint8_t*>(t->d_tblob);
-        a.batch = batch;
-        a.d = P.d;
-        a.n = P.n;
-        a.n_af = L.n_af;
-        a.kind = L.kind;
-        a.phase = op.phase;
+        a.ebuf = t->bb.d_ebuf.as<float>();
+        a.blob = c->d_blob.as<const uint8_t>();
+        a.tblob = t->d_tblob.as<const uint8_t>();
         a.net = t->nets[op.net];
         if (op.net2 >= 0) a.net2 = t->nets[op.net2];
         e = launch_score_net(P.ht, t->net_nh[op.net], t->amode, op.net2 >= 0, a, (unsigned)grid, op.lds, st);
@@ -1357,7 +1375,7 @@ int df_train_logpdf_grad(df_train* t, const float* x, const float* theta, float*
     }
     // 4. raw θ: the chain rule of normalize_input
     if (grad_theta && flow) {
-        e = launch_score_theta_raw(grad_theta, c->d_bounds, c->d_bounds + P.n, P.n, batch, st);
+        e = launch_score_theta_raw(grad_theta, bounds, bounds + P.n, P.n, batch, st);
         if (e != hipSuccess) return hip_err(e, "θ gradient scaling launch");
     }
     return DF_OK;
@@ -1379,8 +1397,9 @@ int df_train_apply(df_train* t, void* stream) {
             return set_err(DF_ERR_NONFINITE, msg);
         }
     }
-    hipError_t e = launch_adam(t->d_params, t->d_grad, t->d_m, t->d_v, t->P, t->opt.eta, t->opt.beta1,
-                               t->opt.beta2, t->opt.epsilon, t->d_bt, st);
+    hipError_t e = launch_adam(t->d_params.as<float>(), t->d_grad.as<const float>(), t->d_m.as<float>(),
+                               t->d_v.as<float>(), t->P, t->opt.eta, t->opt.beta1, t->opt.beta2, t->opt.epsilon,
+                               t->d_bt.as<float>(), st);
     if (e != hipSuccess) return hip_err(e, "Adam kernel launch");
     return repack(t, st);
 }
@@ -1489,7 +1508,7 @@ int df_train_get_params(df_train* t, float* host_out, int64_t count) {
     DeviceGuard gd(t->c->device);
     if (count == 0) return DF_OK;
     hipError_t e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(host_out, t->d_params, sizeof(float) * count, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(host_out, t->d_params.get(), sizeof(float) * count, hipMemcpyDeviceToHost);
     return e == hipSuccess ? DF_OK : hip_err(e, "hipMemcpy(params)");
 }
 
@@ -1499,7 +1518,7 @@ int df_train_set_params(df_train* t, const float* host_in, int64_t count) {
     DeviceGuard gd(t->c->device);
     if (count == 0) return DF_OK;
     hipError_t e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(t->d_params, host_in, sizeof(float) * count, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(t->d_params.get(), host_in, sizeof(float) * count, hipMemcpyHostToDevice);
     if (e != hipSuccess) return hip_err(e, "hipMemcpy(params)");
     int rc = repack(t, nullptr);
     if (rc != DF_OK) return rc;

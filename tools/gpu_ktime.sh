@@ -1,7 +1,9 @@
 #!/bin/bash
 # GPU box: per-kernel average time of one workload under several library builds.
 #   tools/gpu_ktime.sh <tag> "<bench args>" "<kernel regex>" <lib> [<lib> ...]
-# Extra environment for the bench (e.g. DF_TRAIN_NOMERGE=1) is inherited.
+# Extra environment for the bench is inherited.  The sweep form is no environment switch:
+# unmerged dW / front launches are DF_SWEEP_LAYERWISE | DF_SWEEP_SEPARATE of
+# df_train_create_ex (HIPTrainer(sweep=...)).
 set -o pipefail
 cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
