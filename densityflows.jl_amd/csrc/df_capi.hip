@@ -98,6 +98,10 @@ static bool use_small(const df_chain* c, int64_t batch) {
     const df::Plan& P = c->plan;
     if (!(P.uniform && P.fast && P.outv && P.ht == 1 && P.n + P.d <= 8 && P.n_layers <= df::kSmallLayers))
         return false;
+    // A chain of NormalizationLayers only has no conditioner and a 16-byte blob; the small
+    // kernel loads a net's fragments (about 1.1 KiB from the blob's start) for every layer,
+    // used or not, so such a chain stays on the FAST kernel, which loads none.
+    if (P.stages.empty()) return false;
     const int64_t max_b = c->small_max >= 0 ? c->small_max : (int64_t)df::kSmallSamples * 8 * c->n_cu;
     return batch <= max_b;
 }

@@ -668,7 +668,7 @@ int build_plan(const df_chain_desc* desc, Plan* out, std::string* err, int exact
         // Whole chain in one stage when it is small (loaded once per workgroup);
         // otherwise 24 KiB stages, double-buffered in LDS, one net per stage
         // whenever a net fits.
-        int64_t total_bytes = 0;
+        int64_t total_bytes = 0, biggest_net = 0;
         for (int li = 0; li < desc->n_layers; ++li) {
             const df_layer_desc& L = desc->layers[li];
             if (L.kind == DF_LAYER_NORM) continue;
@@ -689,8 +689,10 @@ int build_plan(const df_chain_desc* desc, Plan* out, std::string* err, int exact
                 }
                 return b;
             };
-            if (L.kind == DF_LAYER_RNVP) total_bytes += net_bytes(L.s_net, L.n_dense_s);
-            total_bytes += net_bytes(L.t_net, L.n_dense_t);
+            const int64_t sb = L.kind == DF_LAYER_RNVP ? net_bytes(L.s_net, L.n_dense_s) : 0;
+            const int64_t tb = net_bytes(L.t_net, L.n_dense_t);
+            total_bytes += sb + tb;
+            biggest_net = std::max(biggest_net, std::max(sb, tb));
         }
         // Wide conditioners (>= 128 hidden) run one 16-sample tile per wave, so the
         // stage-switch barrier is amortised over the MFMAs of one stage: give them
@@ -705,6 +707,10 @@ int build_plan(const df_chain_desc* desc, Plan* out, std::string* err, int exact
             const int room = (160 * 1024 - state - round_up(tab_ints * 4, 16) - 1024) / 2;
             cap = std::max(kStageCap, std::min(kBigStageCap, room / kStageAlign * kStageAlign));
         }
+        // The specialised kernel needs every net whole in one stage.  A hidden-64 net with an
+        // MFMA output Dense and 13-16 inputs is 24.5 KiB (at most 28.6 KiB with 32 outputs):
+        // the stage grows to hold it, as the SPLIT packing's does (build_split).
+        if (uniform_shape) cap = std::max(cap, round_up((int)biggest_net, kStageAlign));
         if (const char* e = std::getenv("DF_STAGE_KB")) cap = std::max(4, std::atoi(e)) * 1024;
         Packer pk(P, total_bytes <= kSingleStageCap ? kSingleStageCap : cap);
         const int zero_slot = n + d;

@@ -195,7 +195,7 @@ def test_gradient_parity_exact_f32(cuda, monkeypatch, name, B):
 
 
 @pytest.mark.parametrize("recompute", [False, True])
-@pytest.mark.parametrize("name,B", [("wide", 700), ("wide", 5), ("cfg5", 300)])
+@pytest.mark.parametrize("name,B", [("wide", 700), ("wide", 5), ("cfg5", 300), ("cfg5_in52", 300), ("cfg5_in52", 5)])
 def test_gradient_parity_layerwise_wide(cuda, monkeypatch, name, B, recompute):
     """Conditioners beyond the fused kernel (hidden 128/256, 3 hidden Denses, MFMA
     outputs): the layer-wise path is selected automatically.  By default the
@@ -254,12 +254,29 @@ def _cfg5_in40_spec(rng):
 SPECS["cfg5_in40"] = (_cfg5_in40_spec, 32, 24)
 
 
+def _cfg5_in52_spec(rng):
+    """One config-5-sized block whose first Dense takes 52 inputs (d = 16, n = 44: 8 identity
+    dims + 44 conditions, 8 transformed dims, n + d = 60 <= 64): the reverse sweep's x̄ = W0ᵀδ0
+    runs apart from the W1ᵀδ1 launch.  w1t_delta_xbar (df_train_capi.hip) keeps W0ᵀ resident
+    beside the 96 KiB of SPLIT W1ᵀ chunk buffers; with 49-64 inputs W0ᵀ has four 16-row tiles,
+    so its split planes cost 8 · 4 · 3 KiB = 96 KiB and its f32 fragments 4 · 16 · 1 KiB =
+    64 KiB: 96 + 64 KiB (+ 64 B of column table) passes the 160 KiB of LDS, the function
+    returns false, and a plain δ0 launch is followed by an x̄-only product.  (40 inputs: three
+    tiles, 96 + 48 KiB, resident.)"""
+    return {"kind": "chain", "layers": [
+        O.coupling_block(rng, O.coupling_axes_cut(16, n=44), hidden=256, bias_scale=0.1, out_scale=0.1)]}
+
+
+SPECS["cfg5_in52"] = (_cfg5_in52_spec, 16, 44)
+
+
 @pytest.mark.parametrize("name,sweep,want", [
     ("readme", "AUTO", "FUSED"), ("cfg2", "AUTO", "FUSED"), ("mixed", "AUTO", "FUSED"),
     ("readme", "LAYERWISE", "RECOMPUTE"), ("cfg2", "LAYERWISE", "RECOMPUTE"),
     ("wide", "AUTO", "KEPT"), ("wide", "RECOMPUTE", "RECOMPUTE"),
     ("cfg5", "AUTO", "H0FREE"), ("cfg5", "LAYERWISE", "H0FREE"), ("cfg5", "KEPT", "KEPT"),
     ("cfg5", "RECOMPUTE", "RECOMPUTE"), ("cfg5_in40", "AUTO", "KEPT"),
+    ("cfg5_in52", "AUTO", "KEPT"), ("cfg5_in52", "RECOMPUTE", "RECOMPUTE"), ("cfg5_in52", "H0FREE", None),
     ("cfg5", "FUSED", None), ("wide", "H0FREE", None), ("cfg5_in40", "H0FREE", None), ("cfg2", "KEPT", None)])
 def test_sweep_form_per_shape(cuda, name, sweep, want):
     """Which reverse sweep each conditioner shape takes (df_train_sweep):

@@ -126,6 +126,38 @@ def test_plan_config4():
     assert info.hidden_tiles == 16 and info.n_stages > 16
 
 
+def _edge_cases():
+    import edge_cases as E
+
+    return E
+
+
+@pytest.mark.parametrize("name", list(_edge_cases().CASES) + list(_edge_cases().NORM_ONLY))
+def test_plan_edge_matrix_kernels(name, monkeypatch):
+    """Every chain of the batch-edge matrix (tests/edge_cases.py) plans, without a device,
+    onto the kernel family it is there to cover.  `slowcopy_d12` is a default-shape
+    hidden-64 chain whose nets (15 inputs, MFMA output Dense) are 24.5 KiB each, past the
+    24 KiB stage: the stage grows to hold a net whole (such a chain used to be refused
+    with "internal: default-shape net split across stages").  The chains of one
+    NormalizationLayer plan with no stage at all."""
+    E = _edge_cases()
+    for k in ("DF_F32_EXACT", "DF_NO_WIDE", "DF_FORCE_GENERIC", "DF_NO_FAST", "DF_NO_FOLD", "DF_STAGE_KB"):
+        monkeypatch.delenv(k, raising=False)
+    entry = E.CASES.get(name)
+    for k, v in (entry[3] if entry else {}).items():
+        monkeypatch.setenv(k, v)
+    info = hip.validate(spec_to_element(E.case_spec(name)).layers)
+    if entry is None:
+        assert info.kernel == 3 and info.n_stages == 0 and info.hidden_tiles == 1
+        return
+    assert info.kernel in entry[4], (name, info.kernel)
+    assert (info.d, info.n) == (entry[1], entry[2])
+    if name == "slowcopy_d12":
+        assert info.hidden_tiles == 4 and info.n_stages == 5      # one net per stage
+    if name == "generic_h256":
+        assert info.hidden_tiles == 16 and info.samples_per_block == 128   # K-chunked stages, one tile
+
+
 def test_doctest_summaries():
     # src/Layers.jl:99-104 and src/Blocks.jl:51-59
     s = dfa.summarize(dfa.CouplingLayer(3, [1, 3], n=2, hidden_dim=10, n_sublayers_s=1, σ="tanh"))

@@ -135,6 +135,33 @@ def test_fp32_oracle_within_parity_tolerance(name):
     assert close(x32, g["x_fwd"])[0] and close(l32, g["ldj_fwd"])[0]
 
 
+def _edge_case_names():
+    import edge_cases as E
+
+    return list(E.CASES) + list(E.NORM_ONLY)
+
+
+@pytest.mark.parametrize("name", _edge_case_names())
+def test_edge_cases_fp32_oracle(name):
+    """The chains and inputs of the batch-edge matrix (tests/edge_cases.py, run on the GPU
+    by test_gpu_batch_edges.py): the oracle's own fp32 evaluation of forward, inverse and
+    logpdf keeps the 1e-5 criterion against fp64 with a violation ratio of at most 0.5 at
+    the largest batch — the tolerance is one the reference arithmetic alone keeps, with
+    room to spare, on these weights and inputs."""
+    import edge_cases as E
+
+    D = E.case_data(name)
+    spec, th = D["spec"], D["th"]
+    x32, l32 = O.forward(spec, D["z"], th, np.float32)
+    z32, lb32 = O.backward(spec, D["x_in"], th, np.float32)
+    lp32 = O.flow_logpdf(spec, D["x_in"], th, np.float32)
+    for key, got, want in (("x", x32, D["x"]), ("ldj", l32, D["ldj"]), ("z", z32, D["zb"]),
+                           ("ldj_bwd", lb32, D["ldj_b"]), ("logpdf", lp32, D["lp"])):
+        assert np.all(np.isfinite(want))
+        r = close(got, want, 1e-5)[1]
+        assert r <= 0.5, f"{name} {key}: fp32 oracle violation ratio {r}"
+
+
 def test_logpdf_matches_mvnormal():
     rng = np.random.default_rng(3)
     z = rng.standard_normal((5, 7))
