@@ -244,6 +244,20 @@ void build_split(const df_chain_desc* desc, Plan& P, const std::vector<char>& fo
         ULayer& U = P.sulayers[li];
         if (L.kind == DF_LAYER_RNVP) pack(L.s_net, DL.s_dense0, &U.s);
         pack(L.t_net, DL.t_dense0, &U.t);
+        // what the kernel no longer loads: the slot words (df_plan.h) stand for the
+        // layer's table entries, and a net's hidden and output Dense follow from off_w0
+        for (int g = 0; g < 4; ++g) {
+            const int32_t f = P.tables[U.feat_tab + g], a = P.tables[U.af_tab + (g < U.n_af ? g : 0)];
+            if (f < 0 || f >= (1 << kSplitSlotBits) || a < 0 || a >= (1 << kSplitSlotBits))
+                fail(DF_ERR_UNSUPPORTED, "SPLIT plan: a state slot does not fit the 8 bits of a slot word");
+        }
+        U.feat_word = split_feat_word(P.tables.data(), U);
+        U.af_word = split_af_word(P.tables.data(), U);
+        for (const UNet* u : {&U.s, &U.t}) {
+            if (u == &U.s && L.kind != DF_LAYER_RNVP) continue;
+            if (u->off_h != u->off_w0 + kSplitOffH(ht) || u->off_out != u->off_w0 + kSplitOffOut(ht))
+                fail(DF_ERR_INVALID, "internal: SPLIT net layout differs from kSplitOffH / kSplitOffOut");
+        }
     }
     close();
     auto sched = [&](bool fwd) {

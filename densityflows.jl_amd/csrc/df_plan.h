@@ -104,10 +104,34 @@ struct UNet {
 
 struct ULayer {
     int32_t kind, elem_start, elem_end, n_af;
-    int32_t feat_tab, af_tab, norm_off, pad0;
-    float alpha, beta, ldj_const, pad1;
+    int32_t feat_tab, af_tab, norm_off;
+    int32_t feat_word;   // SPLIT plans: split_feat_word (0 otherwise)
+    float alpha, beta, ldj_const;
+    int32_t af_word;     // SPLIT plans: split_af_word (0 otherwise)
     UNet s, t;
 };
+static_assert(sizeof(ULayer) == 12 * 4 + 2 * sizeof(UNet), "ULayer: the slot words take the former pads");
+
+// The slot words of a SPLIT layer (its s- and t-net share both tables): what lane group
+// g = 0..3 of the specialised SPLIT kernel reads from the tables, 8 bits each, so that a
+// net body takes them from a scalar register (shift by 8·g, mask) and not from LDS.
+//   feat word: tables[feat_tab + g], the state column of first-Dense input g (g = 3: the
+//              folded-bias column)
+//   af word:   tables[af_tab + (g < n_af ? g : 0)], the transformed dim lane group g
+//              updates (groups past n_af read entry 0 and store nothing)
+// Every slot is a state column, below the state stride <= kMaxState + 4.
+constexpr int kSplitSlotBits = 8;
+inline int32_t split_feat_word(const int32_t* tables, const ULayer& U) {
+    uint32_t w = 0;
+    for (int g = 0; g < 4; ++g) w |= (uint32_t)(tables[U.feat_tab + g] & 0xff) << (kSplitSlotBits * g);
+    return (int32_t)w;
+}
+inline int32_t split_af_word(const int32_t* tables, const ULayer& U) {
+    uint32_t w = 0;
+    for (int g = 0; g < 4; ++g)
+        w |= (uint32_t)(tables[U.af_tab + (g < U.n_af ? g : 0)] & 0xff) << (kSplitSlotBits * g);
+    return (int32_t)w;
+}
 
 // Wide-net kernel (df_wide_impl.h): every conditioner is Dense(in <= 64, 256) →
 // Dense(256, 256) → Dense(256, out <= 32).  Its weights live in their own blob of
@@ -187,6 +211,10 @@ DF_HD inline uint16_t bf16_split_plane(float w, int plane) {
 //   output Dense f32 [n_out][16·HT] then b[4] (VALU GEMV, as in the f32 layout)
 constexpr int kSplitFirstBytes(int ht) { return ht * 1024; }
 constexpr int kSplitHiddenBytes(int ht) { return (ht / 2) * ht * 3 * 1024; }
+// The hidden and the output Dense from the net's start: the specialised SPLIT kernel
+// derives them from UNet::off_w0 (build_split checks UNet::off_h / off_out against these).
+constexpr int kSplitOffH(int ht) { return kSplitFirstBytes(ht); }
+constexpr int kSplitOffOut(int ht) { return kSplitFirstBytes(ht) + kSplitHiddenBytes(ht) + 4 * 16 * ht; }
 
 struct Plan {
     int d = 0, n = 0, n_layers = 0;

@@ -748,52 +748,89 @@ __device__ __forceinline__ void out_valu_t_pf(const uint8_t* w3g, const f32x4 (&
     }
 }
 
+// What a net body of the read-ahead SPLIT path takes from the descriptors, as values the
+// kernel loads once per net into scalar registers (run_net), outside the tile-group loop:
+// the net's start in its stage and the layer's two slot words (df_plan.h).
+struct SplitHead {
+    int off_w0, feat_word, af_word;
+};
+// the read-ahead SPLIT path of net_tiles (diagnostic builds keep the straight form)
+#if DF_SPLIT_PREFETCH && !defined(DF_EXP_NOTAIL) && !defined(DF_DIAG_NOSPLIT)
+#define DF_SPLIT_HEAD_REGS 1
+#else
+#define DF_SPLIT_HEAD_REGS 0
+#endif
+
+// Wave priority by phase of a read-ahead SPLIT body (DF_SPLIT_PRIO): 1, the default,
+// raises a wave (s_setprio 2) from the first product MFMA of its first Dense to the last
+// MFMA of its hidden Dense and drops it to 0 for the rest — the VALU tail (second relu,
+// output GEMV, coupling), the ldj update, the next head's request and any stage switch —
+// so that a wave with matrix work issues first and a wave in its tail takes the gaps
+// between another wave's MFMAs: 1.329 -> 1.246 M cycles per config-2 launch.  2 is the
+// opposite assignment, the control (1.380); 0 sets no priority.  Levels 1 and 3 measure as
+// 2 does.  (profiles/head_ab.txt.)
+#ifndef DF_SPLIT_PRIO
+#define DF_SPLIT_PRIO 1
+#endif
+template <bool MATRIX_PHASE>
+__device__ __forceinline__ void split_prio() {
+    if constexpr (DF_SPLIT_PRIO == 1) __builtin_amdgcn_s_setprio(MATRIX_PHASE ? 2 : 0);
+    if constexpr (DF_SPLIT_PRIO == 2) __builtin_amdgcn_s_setprio(MATRIX_PHASE ? 0 : 2);
+}
+
 // Evaluate net N for TT 16-sample tiles (state rows ro[t]) and apply its
 // coupling phase; sum[t] = Σ_k s_k for s phases (row order).
+// hd: the read-ahead SPLIT path's scalar words (SplitHead); unused by every other path.
 template <int HT, int TT, bool OUTV, bool RELU, int PH, bool FAST = false, int NO = 0, bool SPLIT = false>
 __device__ __forceinline__ void net_tiles(const uint8_t* buf, const UNet& N, const ULayer& L, const int32_t* tab,
-                                          float* state, const int (&ro)[TT], float (&sum)[TT]) {
+                                          float* state, const int (&ro)[TT], float (&sum)[TT], const SplitHead& hd) {
     const int lane = threadIdx.x & 63, g = lane >> 4;
     constexpr bool SPH = (PH == impl::PH_S_FWD || PH == impl::PH_S_BWD);
-#if DF_SPLIT_PREFETCH && !defined(DF_EXP_NOTAIL) && !defined(DF_DIAG_NOSPLIT)
+#if DF_SPLIT_HEAD_REGS
     if constexpr (SPLIT && FAST && HT >= 2 && OUTV && NO > 0) {
-        // the table word and the first-Dense fragments in one round trip, then the
-        // features (they need the word) with step 0 of the hidden Dense
-        // (every descriptor word of the body up front: a scalar load placed at its use
-        // is a round trip of its own in the middle of the tail)
+        // The head is ONE request: the first-Dense fragments, the features and step 0 of
+        // the hidden Dense, then one wait, then the first-Dense split and its MFMAs.
+        // Nothing of it depends on a load: the net's start in the stage and the layer's
+        // two slot words (df_plan.h) are scalar registers the caller loaded once per net,
+        // the hidden and the output Dense follow from the start (kSplitOffH /
+        // kSplitOffOut), and a lane group takes its slots from the words by a bit-field
+        // extract.  (With the table word in LDS and every offset a scalar load at its use,
+        // a body made five dependent round trips before its first MFMA:
+        // profiles/head_isa_waits.txt.)
         // lane and g from an opaque copy of the thread id: derived here they die with the
         // body; derived once per kernel every lane offset is a VGPR held across all bodies,
         // which this instance (128 VGPRs) does not have
         int tx = threadIdx.x;
         asm volatile("" : "+v"(tx));
         const int lane = tx & 63, g = lane >> 4;
-        const int off_out = N.off_out, af_tab = L.af_tab;
-        asm volatile("" ::"s"(off_out), "s"(af_tab));
-        const int slot = tab[L.feat_tab + g];
+        const uint8_t* net = buf + hd.off_w0;
+        const int slot = ((uint32_t)hd.feat_word >> (kSplitSlotBits * g)) & ((1 << kSplitSlotBits) - 1);
         bf16x8 w0[HT];
 #pragma unroll
-        for (int m = 0; m < HT; ++m) w0[m] = *reinterpret_cast<const bf16x8*>(buf + N.off_w0 + lane * 16 + m * 1024);
-        sched_fence();
-        lds_wait0();
+        for (int m = 0; m < HT; ++m) w0[m] = *reinterpret_cast<const bf16x8*>(net + lane * 16 + m * 1024);
         float xin[TT][4];
 #pragma unroll
         for (int t = 0; t < TT; ++t) xin[t][0] = state[ro[t] + slot];
-        const uint8_t* wh = buf + N.off_h;
+        const uint8_t* wh = net + kSplitOffH(HT);
         SplitStep f0;
         split_step_request<HT, true>(wh + lane * 16, wh + (HT / 2) * HT * 3072 + (g << 4), 0, f0);
+        sched_fence();
+        lds_wait0();
+        split_prio<true>();
         sched_fence();
         f32x4 A[TT][HT], B[TT][HT];
         dense_first_split_pf<HT, TT>(w0, xin, A);
         bias_act<HT, TT, true>(buf, DF_ACT_RELU, A, false);
         dense_hidden_split_pf<HT, TT>(wh, lane, A, B, f0);
-        // tail: the first output's weights, the bias and the slot word before the
-        // second relu
-        const uint8_t* w3g = buf + off_out + (g << 4);
+        // tail: the first output's weights and the bias before the second relu
+        const uint8_t* w3 = net + kSplitOffOut(HT);
+        const uint8_t* w3g = w3 + (g << 4);
         sched_fence();
+        split_prio<false>();
         f32x4 wo[HT];
         out_row_request<HT, NO>(w3g, 0, wo);
-        const float bo = reinterpret_cast<const float*>(buf + off_out)[NO * 16 * HT + (g < NO ? g : 0)];
-        const int aslot = tab[af_tab + (g < NO ? g : 0)];
+        const float bo = reinterpret_cast<const float*>(w3)[NO * 16 * HT + (g < NO ? g : 0)];
+        const int aslot = ((uint32_t)hd.af_word >> (kSplitSlotBits * g)) & ((1 << kSplitSlotBits) - 1);
         sched_fence();
         bias_act<HT, TT, true>(buf, DF_ACT_RELU, B, false);
         float v[TT], y[TT];
@@ -948,6 +985,7 @@ uniform_kernel(ChainArgs a) {
     sg.sched = FWD ? a.sched_fwd : a.sched_bwd;
     sg.n = FWD ? a.n_sched_fwd : a.n_sched_bwd;
     constexpr bool kLaneLocalDma = SPLIT && DF_SPLIT_PREFETCH;  // df_chain_impl.h dma_stage
+    constexpr bool kSplitHead = SPLIT && FAST && OUTV && HT >= 2 && DF_SPLIT_HEAD_REGS;  // net_tiles' read-ahead path
     impl::stager_start<kLaneLocalDma>(sg, a);
 
     // Copy-in of the tables, the NormalizationLayer bounds (a.params, kept in LDS right
@@ -1112,7 +1150,8 @@ uniform_kernel(ChainArgs a) {
             const bool rnvp = (kind == DF_LAYER_RNVP);
             // this wave's tiles in groups of kTT (nt is a multiple of kTT)
             constexpr int kTT = FAST ? kFastTileGroup : kUniformTileGroup;
-            auto tiles_loop = [&](const UNet& N, auto ph_tag, auto no_tag, bool sphase, float sign) {
+            auto tiles_loop = [&](const UNet& N, const SplitHead& hd, auto ph_tag, auto no_tag, bool sphase,
+                                  float sign) {
                 constexpr int PH = decltype(ph_tag)::value;
                 constexpr int NO = decltype(no_tag)::value;
                 const uint8_t* buf = sg.buf();
@@ -1130,7 +1169,7 @@ uniform_kernel(ChainArgs a) {
                     if constexpr (SPLIT) asm volatile("" : "+v"(r0));
 #pragma unroll
                     for (int t = 0; t < kTT; ++t) ro[t] = r0 + (tt + t) * tstep;
-                    net_tiles<HT, kTT, OUTV, RELU, PH, FAST, NO, SPLIT>(buf, N, L, tab, state, ro, ssum);
+                    net_tiles<HT, kTT, OUTV, RELU, PH, FAST, NO, SPLIT>(buf, N, L, tab, state, ro, ssum, hd);
 #pragma unroll
                     for (int t = 0; t < kTT; ++t) {
                         if (sphase) ldj_update(ro[t], sign * ssum[t], first_in_elem, last_in_elem);
@@ -1139,16 +1178,26 @@ uniform_kernel(ChainArgs a) {
                 }
             };
             auto run_net = [&](const UNet& N, auto ph_tag, bool sphase, float sign) {
-                impl::ensure_stage<kLaneLocalDma>(N.stage, sg, a);
+                // read-ahead SPLIT path: every descriptor word of the net as a value, loaded
+                // here in one round trip before the stage switch and pinned: left at their
+                // uses the scalar loads sink into the tile-group loop, each one a wait of its
+                // own in front of the body's LDS reads
+                SplitHead hd{0, 0, 0};
+                int stage = N.stage, n_out = N.n_out;
+                if constexpr (kSplitHead) {
+                    hd = SplitHead{N.off_w0, L.feat_word, L.af_word};
+                    asm volatile("" : "+s"(stage), "+s"(n_out), "+s"(hd.off_w0), "+s"(hd.feat_word), "+s"(hd.af_word));
+                }
+                impl::ensure_stage<kLaneLocalDma>(stage, sg, a);
                 if constexpr (FAST && OUTV) {  // output count fixed per net: branch-free tails
-                    switch (N.n_out) {
-                        case 1: tiles_loop(N, ph_tag, std::integral_constant<int, 1>{}, sphase, sign); break;
-                        case 2: tiles_loop(N, ph_tag, std::integral_constant<int, 2>{}, sphase, sign); break;
-                        case 3: tiles_loop(N, ph_tag, std::integral_constant<int, 3>{}, sphase, sign); break;
-                        default: tiles_loop(N, ph_tag, std::integral_constant<int, 4>{}, sphase, sign); break;
+                    switch (n_out) {
+                        case 1: tiles_loop(N, hd, ph_tag, std::integral_constant<int, 1>{}, sphase, sign); break;
+                        case 2: tiles_loop(N, hd, ph_tag, std::integral_constant<int, 2>{}, sphase, sign); break;
+                        case 3: tiles_loop(N, hd, ph_tag, std::integral_constant<int, 3>{}, sphase, sign); break;
+                        default: tiles_loop(N, hd, ph_tag, std::integral_constant<int, 4>{}, sphase, sign); break;
                     }
                 } else {
-                    tiles_loop(N, ph_tag, std::integral_constant<int, 0>{}, sphase, sign);
+                    tiles_loop(N, hd, ph_tag, std::integral_constant<int, 0>{}, sphase, sign);
                 }
             };
             using PSF = std::integral_constant<int, impl::PH_S_FWD>;

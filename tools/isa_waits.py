@@ -14,6 +14,12 @@ and one line per net body.  A net body is an innermost loop that holds product M
   exposed  those of lgkm that retire a read issued after the last MFMA before the wait:
            nothing of the wave's own matrix work covers that read's round trip
   nop5     s_nop >= 5 directly before a ds_read (an MFMA operand overwritten too early)
+  head     s_waitcnt before the body's first product MFMA: the dependent round trips
+           (scalar cache or LDS) a wave makes before it has matrix work
+  s_load   scalar loads inside the body (descriptor words that were not hoisted)
+
+and per kernel the v_writelane / v_readlane moves (SGPR spills to VGPR lanes) and how many
+of them lie inside a loop that holds a net body (the layer loop and everything in it).
 
 LDS and scalar-memory operations retire in issue order for this count (the compiler
 waits lgkmcnt(0) whenever a scalar load is outstanding, which the model reproduces).
@@ -25,6 +31,8 @@ import sys
 DEFAULT = r"uniform_kernelILi4ELi[0-3]ELb1ELb1ELb1ELb1E"
 LABEL = re.compile(r"^(\.LBB\d+_\d+):")
 BRANCH = re.compile(r"^\s+s_cbranch_\w+\s+(\.LBB\d+_\d+)")
+ANY_BRANCH = re.compile(r"^\s+s_c?branch\w*\s+(\.LBB\d+_\d+)")
+LANE_MOVE = re.compile(r"^\s+v_(writelane|readlane)_b32\b")
 LGKM = re.compile(r"lgkmcnt\((\d+)\)")
 
 
@@ -66,6 +74,41 @@ def bodies(lines, a, b):
             loops.append((at[m.group(1)], i))
     inner = [l for l in loops if not any(o != l and l[0] <= o[0] and o[1] <= l[1] for o in loops)]
     return [l for l in inner if any("v_mfma_f32_16x16x32" in lines[i] for i in range(l[0], l[1]))]
+
+
+def lane_moves(lines, a, b, net_bodies):
+    """(all v_writelane / v_readlane of the kernel, those inside a loop that holds a net body)."""
+    at, loops = {}, []
+    for i in range(a, b):
+        m = LABEL.match(lines[i])
+        if m:
+            at[m.group(1)] = i
+            continue
+        m = ANY_BRANCH.match(lines[i])
+        if m and m.group(1) in at:
+            loops.append((at[m.group(1)], i))
+    outer = [l for l in loops if any(l[0] <= nb[0] and nb[1] <= l[1] and l != nb for nb in net_bodies)]
+    outer += list(net_bodies)
+    moves = [i for i in range(a, b) if LANE_MOVE.match(lines[i])]
+    inside = [i for i in moves if any(l[0] <= i <= l[1] for l in outer)]
+    return len(moves), len(inside)
+
+
+def head_line(lines, a, b):
+    """(s_waitcnt before the first product MFMA of the body, scalar loads in the body)."""
+    head, seen, s_loads = 0, False, 0
+    for i in range(a, b + 1):
+        ln = lines[i].split(";")[0].strip()
+        if not ln or ln.endswith(":") or ln.startswith("."):
+            continue
+        op = ln.split()[0]
+        if op.startswith("v_mfma") and "16x16x32" in op:
+            seen = True
+        elif op == "s_waitcnt" and not seen:
+            head += 1
+        elif op.startswith("s_load") or op.startswith("s_buffer_load"):
+            s_loads += 1
+    return head, s_loads
 
 
 def body_line(lines, a, b):
@@ -123,12 +166,20 @@ def main():
         s = stats(lines, a, b)
         print(f"{name}: VGPRs {s.get('NumVgprs')} scratch {s.get('ScratchSize')} occupancy {s.get('Occupancy')}")
         tot = [0, 0, 0, 0]
-        for k, (la, lb) in enumerate(bodies(lines, a, b)):
+        heads, loads = [], 0
+        net_bodies = bodies(lines, a, b)
+        for k, (la, lb) in enumerate(net_bodies):
             runs, waits, lgkm, exposed, nop5 = body_line(lines, la, lb)
+            head, s_loads = head_line(lines, la, lb)
+            heads.append(head)
+            loads += s_loads
             tot = [x + y for x, y in zip(tot, (waits, lgkm, exposed, nop5))]
             print(f"  body {k} lines {la + 1}-{lb + 1}: runs {runs} waits {waits} lgkm {lgkm} "
-                  f"exposed {exposed} nop5 {nop5}")
-        print(f"  all bodies: waits {tot[0]} lgkm {tot[1]} exposed {tot[2]} nop5 {tot[3]}")
+                  f"exposed {exposed} nop5 {nop5} head {head} s_load {s_loads}")
+        print(f"  all bodies: waits {tot[0]} lgkm {tot[1]} exposed {tot[2]} nop5 {tot[3]} "
+              f"head {sorted(set(heads))} s_load {loads}")
+        n_moves, n_inside = lane_moves(lines, a, b, net_bodies)
+        print(f"  v_writelane/v_readlane: {n_moves}, inside the layer loop: {n_inside}")
     if not found:
         print(f"no kernel matches {args.kernel}", file=sys.stderr)
         return 1
