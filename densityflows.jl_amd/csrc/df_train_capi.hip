@@ -14,6 +14,7 @@
 
 #include "df_handle.h"
 #include "df_ltrain.h"
+#include "df_pack.h"
 #include "df_train.h"
 
 using namespace df;
@@ -189,21 +190,12 @@ int64_t pack_wt_planes(const Plan& P, int rows, int kdim, int mt, int chunks, in
                        std::vector<uint8_t>& blob, std::vector<int32_t>& dst, std::vector<int32_t>& src) {
     const int64_t base = (int64_t)blob.size();
     blob.resize(blob.size() + (size_t)chunks * mt * 3072, 0);
-    for (int c = 0; c < chunks; ++c)
-        for (int m = 0; m < mt; ++m)
-            for (int p = 0; p < 3; ++p)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int e = 0; e < 8; ++e) {
-                        const int i = 16 * m + (lane & 15), g = lane >> 4;
-                        const int k = 32 * c + 16 * (e >> 2) + 4 * g + (e & 3);
-                        if (i >= rows || k >= kdim) continue;
-                        const int64_t from = w_off + k + (int64_t)ldw * i;
-                        const int64_t at = base + ((((int64_t)c * mt + m) * 3 + p) * 64 + lane) * 16 + 2 * e;
-                        const uint16_t h = bf16_split_plane(P.trainables[from], p);
-                        std::memcpy(&blob[at], &h, 2);
-                        dst.push_back((int32_t)at);
-                        src.push_back((int32_t)(from * 4 + p));
-                    }
+    pack::ParamSink<uint8_t> sink(blob, dst, src, pack::ParamSink<uint8_t>::PLANES);
+    pack::for_each_plane_frag(0, chunks, 0, mt, pack::k_plane_hidden, [&](int64_t pos, int i, int k, int p) {
+        if (i >= rows || k >= kdim) return;
+        const int32_t from = (int32_t)(w_off + k + (int64_t)ldw * i);
+        sink.plane(base + pos, p, {from, P.trainables[from]});
+    });
     return base;
 }
 
@@ -219,21 +211,13 @@ LOp pack_lop(df_train* t, const Plan& P, const LDense& D, bool transposed) {
     op.frag = (int64_t)t->lblob.size();
     const size_t bytes = (size_t)op.nkq * op.mt * 1024;
     t->lblob.resize(t->lblob.size() + bytes, 0);
-    float* f = reinterpret_cast<float*>(t->lblob.data() + op.frag);
-    const int64_t f0 = op.frag / 4;
-    for (int kq = 0; kq < op.nkq; ++kq)
-        for (int m = 0; m < op.mt; ++m)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int r = 0; r < 4; ++r) {
-                    const int i = 16 * m + (lane & 15), k = 16 * kq + 4 * (lane >> 4) + r;
-                    if (i >= rows || k >= kdim) continue;
-                    const int orow = transposed ? k : i, icol = transposed ? i : k;  // W[orow, icol]
-                    const int64_t src = D.w_off + orow + (int64_t)D.out_dim * icol;
-                    const int64_t q = (((int64_t)kq * op.mt + m) * 64 + lane) * 4 + r;
-                    f[q] = P.trainables[src];
-                    t->ldst.push_back((int32_t)(f0 + q));
-                    t->lsrc.push_back((int32_t)src);
-                }
+    pack::ParamSink<uint8_t> sink(t->lblob, t->ldst, t->lsrc, pack::ParamSink<uint8_t>::WORDS);
+    pack::for_each_f32_frag(0, op.nkq, op.mt, pack::k_hidden_quad, [&](int64_t q, int i, int k) {
+        if (i >= rows || k >= kdim) return;
+        const int orow = transposed ? k : i, icol = transposed ? i : k;  // W[orow, icol]
+        const int32_t src = (int32_t)(D.w_off + orow + (int64_t)D.out_dim * icol);
+        sink.f32(op.frag + 4 * q, {src, P.trainables[src]});
+    });
     // SPLIT planes of a hidden-256 Wᵀ (the ldense_kernel SPLIT instances), and of a first
     // Dense's W0ᵀ over a 256-wide hidden layer (≤ 64 conditioner inputs: the x̄ product
     // of the SPLIT W1ᵀδ1 epilogue)
