@@ -159,6 +159,8 @@ SIGNATURES = {
     "df_train_step_dist": (C.c_int, [_VP, _VP, _VP, _VP, _I64, _I64, _VP, _VP]),
     "df_flow_sample": (C.c_int, [_VP, _VP, _VP, C.c_int, _I64, C.c_uint64, C.c_uint64, _VP]),
     "df_random_normal": (C.c_int, [_VP, _I64, C.c_uint64, C.c_uint64, _VP]),
+    "df_flow_logpdf_grid": (C.c_int, [_VP, _VP, C.POINTER(_I64), _I64, _I64, _VP, _I64, _VP]),
+    "df_theta_broadcast": (C.c_int, [_VP, _VP, C.c_int, _I64, _VP]),
     "df_chain_clock_probe": (C.c_int, [_VP, C.c_int]),
     "df_chain_clock_read": (C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_I64)]),
     "df_device_alloc": (C.c_int, [C.POINTER(_VP), C.c_size_t]),

@@ -118,6 +118,9 @@ struct df_chain {
     // θ broadcast workspace of df_flow_sample (NTuple θ), which allocates and grows it itself
     float* d_theta_ws = nullptr;
     int64_t theta_ws_cap = 0;
+    // staging of df_flow_logpdf_grid: one chunk's [x (d, chunk) | θ (n, chunk)]; only grows
+    DevBuf d_grid_ws;
+    int64_t grid_ws_cap = 0;  // floats
     ~df_chain() {
         if (d_theta_ws) (void)hipFree(d_theta_ws);
     }

@@ -95,6 +95,19 @@ int df_random_normal(float* out, int64_t count, uint64_t seed, uint64_t offset, 
     return e == hipSuccess ? DF_OK : hip_err(e, "normal_kernel launch");
 }
 
+int df_theta_broadcast(float* out, const float* theta, int n, int64_t batch, void* stream) {
+    if (n < 0 || batch < 0) return set_err(DF_ERR_SHAPE, "negative size");
+    const int64_t need = (int64_t)n * batch;
+    if (need == 0) return DF_OK;
+    if (!out || !theta) return set_err(DF_ERR_INVALID, "null pointer");
+    const int64_t blocks = (need + 255) / 256;
+    if (blocks > 0x7fffffff) return set_err(DF_ERR_UNSUPPORTED, "batch too large for one launch");
+    hipLaunchKernelGGL(df::broadcast_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, out, theta, n,
+                       batch);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? DF_OK : hip_err(e, "broadcast_kernel launch");
+}
+
 int df_flow_sample(df_chain* c, float* x_out, const float* theta_raw, int theta_broadcast, int64_t batch,
                    uint64_t seed, uint64_t offset, void* stream) {
     if (!c) return set_err(DF_ERR_INVALID, "null chain");

@@ -13,8 +13,8 @@ from .chains import FlowChain, _n_of
 from .data import DataArrays, MetaData, maximum_theta, minimum_theta
 from .hip import as_julia_device, julia_empty
 
-__all__ = ["Flow", "MvNormal", "predict", "sample", "logpdf", "logpdf_grad", "pdf", "training_loss",
-           "validation_loss", "nll_partial_sum"]
+__all__ = ["Flow", "MvNormal", "predict", "sample", "logpdf", "logpdf_grid", "logpdf_grad", "pdf",
+           "training_loss", "validation_loss", "nll_partial_sum"]
 
 LOG2PI = float(np.log(2.0 * np.pi))
 
@@ -79,12 +79,17 @@ class Flow:
     def forward_(self, z, theta=None):
         return self.hip().apply_inplace(z, self._theta(theta, z), flow=True)
 
-    def _theta(self, theta, y):
+    def _theta(self, theta, y, device: bool = False):
+        """θ as the array-level call takes it.  An NTuple θ is broadcast to (n, dims...):
+        ``device=True`` (logpdf, pdf, nll_partial_sum) leaves it on the device, filled by
+        ``df_theta_broadcast``; otherwise it comes back as ``y`` is (numpy for numpy)."""
         if self.n == 0:
             return None
         if theta is None:
             raise _lib.DimensionMismatch("dimensions θ must match (n, dims...) with n number of trained parameters")
         if isinstance(theta, tuple):  # NTuple θ: one condition for every point
+            if device:
+                return _broadcast_theta_device(self.hip(), theta, tuple(y.shape[1:]), y)
             return _broadcast_theta(theta, tuple(y.shape[1:]), y)
         return theta
 
@@ -99,6 +104,18 @@ def _broadcast_theta(theta: tuple, dims, like):
     buf.view(-1, len(theta)).copy_(t.expand(buf.numel() // len(theta), len(theta)))
     if not isinstance(like, torch.Tensor):
         return view.cpu().numpy()
+    return view
+
+
+def _broadcast_theta_device(h, theta: tuple, dims, like):
+    """``_broadcast_theta`` without the host: the (n, dims...) array stays a device tensor."""
+    import torch
+
+    dev = like.device if isinstance(like, torch.Tensor) and like.device.type == "cuda" else h.device
+    buf, view = julia_empty(len(theta), tuple(dims), dev)
+    t = torch.tensor([float(np.float32(v)) for v in theta], dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        h.run_theta_broadcast(buf, t, buf.numel() // max(len(theta), 1))
     return view
 
 
@@ -147,8 +164,105 @@ def sample(flow: Flow, dims: Union[int, Tuple[int, ...]], theta=None, rng=None, 
 
 def logpdf(flow: Flow, x, theta=None):
     """``logpdf(flow, x, θ)`` — src/Flows.jl:272-284: backward + base logpdf + ldj (fused)."""
-    th = flow._theta(theta, x)
+    if isinstance(x, tuple):
+        return _logpdf_axes(flow, x, theta)
+    th = flow._theta(theta, x, device=True)
     return flow.hip().logpdf(x, th)
+
+
+def _axis_values(a, what):
+    """One grid axis as (values, is_tensor): a float32 vector, numpy or torch."""
+    import torch
+
+    if isinstance(a, torch.Tensor):
+        if a.dim() != 1:
+            raise _lib.DimensionMismatch(f"{what} must be a vector, got size {tuple(a.shape)}")
+        return a.detach().to(torch.float32), True
+    a = np.asarray(a, dtype=np.float32)
+    if a.ndim != 1:
+        raise _lib.DimensionMismatch(f"{what} must be a vector, got size {a.shape}")
+    return a, False
+
+
+def _grid_eval(flow: Flow, x_axes, theta_axes, first, count, chunk):
+    """Shared by logpdf_grid and the tuple-x logpdf → (flat device values, lens, numpy out?,
+    whole grid?)."""
+    import torch
+
+    h = flow.hip()
+    d, n = flow.d, flow.n
+    x_axes = tuple(x_axes)
+    theta_axes = tuple(theta_axes) if theta_axes is not None else ()
+    if len(x_axes) != d:
+        raise _lib.DimensionMismatch(f"a grid in x needs d = {d} vectors, got {len(x_axes)}")
+    if len(theta_axes) != n:
+        raise _lib.DimensionMismatch(f"a grid needs n = {n} entries of θ (values or vectors), got {len(theta_axes)}")
+    parts, any_tensor = [], False
+    for k, a in enumerate(x_axes):
+        v, is_t = _axis_values(a, f"x axis {k + 1}")
+        parts.append(v)
+        any_tensor = any_tensor or is_t
+    for k, a in enumerate(theta_axes):
+        if not isinstance(a, torch.Tensor) and np.ndim(a) == 0:
+            a = np.asarray([a], dtype=np.float32)       # one value: an axis of length 1
+        elif isinstance(a, torch.Tensor) and a.dim() == 0:
+            a = a.reshape(1)
+        v, is_t = _axis_values(a, f"θ axis {k + 1}")
+        parts.append(v)
+        any_tensor = any_tensor or is_t
+    lens = tuple(int(v.shape[0]) for v in parts)
+    if any_tensor:
+        axes_buf = torch.cat([v.to(h.device) if isinstance(v, torch.Tensor) else torch.tensor(v, device=h.device)
+                              for v in parts]).contiguous()
+    else:
+        axes_buf = torch.from_numpy(np.concatenate(parts) if parts else np.zeros(0, np.float32)).to(h.device)
+    P = 1
+    for L in lens:
+        P *= L
+    whole = first == 0 and count is None
+    first = int(first)
+    count = P - first if count is None else int(count)
+    if first < 0 or count < 0 or first + count > P:
+        raise _lib.DimensionMismatch(f"window [{first}, {first + count}) outside the grid of {P} points")
+    lpb = torch.empty(count, dtype=torch.float32, device=h.device)
+    with torch.cuda.device(h.device):
+        h.run_logpdf_grid(axes_buf, lens, first, count, lpb, chunk)
+    return lpb, lens, not any_tensor, whole
+
+
+def logpdf_grid(flow: Flow, x_axes, theta_axes=None, first: int = 0, count: Optional[int] = None, chunk: int = 0):
+    """logpdf on the outer product of axis vectors, generated on the device (one library
+    call, ``df_flow_logpdf_grid``): ``x_axes`` are d vectors, ``theta_axes`` n entries,
+    each one raw θ value or a vector of them — a likelihood surface over θ is a grid with
+    x axes of length 1.  Without a window the result has shape (L₁, …, L_d, M₁, …, M_n)
+    (M = 1 for a single value), the first axis varying fastest in memory as in the
+    reference's ``reshape(…, lens...)`` (src/Flows.jl:303-304).  With ``first`` / ``count``
+    it is the flat values of points [first, first + count) of that order: the grid may be
+    far larger than memory, only the window is evaluated.  ``chunk``: points per launch
+    (0: the library's default).  numpy in, numpy out; any device tensor among the axes
+    gives a device tensor."""
+    from .hip import HIPChain, _to_numpy
+
+    lpb, lens, was_np, whole = _grid_eval(flow, x_axes, theta_axes, first, count, chunk)
+    v = HIPChain._ldj_view(lpb, lens) if whole else lpb
+    return _to_numpy(v) if was_np else v
+
+
+def _logpdf_axes(flow: Flow, x: tuple, theta):
+    """``logpdf(flow, (x₁, …, x_d) [, (θ₁, …, θ_n)])`` — src/Flows.jl:287-331."""
+    from .hip import HIPChain, _to_numpy
+
+    if len(x) != flow.d:
+        raise _lib.DimensionMismatch(f"x given as a tuple must hold d = {flow.d} vectors, got {len(x)}")
+    if flow.n == 0:
+        theta = ()
+    elif not isinstance(theta, tuple):
+        raise _lib.DimensionMismatch("if x is given as a tuple of vectors, θ must be passed as an NTuple of n values")
+    if len(theta) != flow.n or any(np.ndim(v) != 0 for v in theta):
+        raise _lib.DimensionMismatch(f"θ must be an NTuple of n = {flow.n} values")
+    lpb, lens, was_np, _ = _grid_eval(flow, x, theta, 0, None, 0)
+    v = HIPChain._ldj_view(lpb, lens[:flow.d])
+    return _to_numpy(v) if was_np else v
 
 
 def logpdf_grad(flow: Flow, x, theta=None, state=None):
@@ -204,7 +318,7 @@ def pdf(flow: Flow, x, theta=None):
 def nll_partial_sum(flow: Flow, x, theta=None, out=None):
     """Σ_j logpdf(x_j) in fp64 on device (deterministic), plus the sample count —
     the per-rank partial of ``loss`` (src/Flows.jl:352-359)."""
-    th = flow._theta(theta, x)
+    th = flow._theta(theta, x, device=True)
     return flow.hip().logpdf_sum(x, th, out=out)
 
 

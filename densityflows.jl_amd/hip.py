@@ -266,6 +266,22 @@ class HIPChain:
                                                C.c_void_p(sumbuf.data_ptr()), C.c_int64(batch),
                                                _stream(self.device)), "logpdf_sum")
 
+    def run_logpdf_grid(self, axes_buf, lens, first: int, count: int, lpbuf, chunk: int = 0):
+        """df_flow_logpdf_grid: logpdf on points [first, first + count) of the outer product of
+        the d + n axis vectors concatenated in ``axes_buf`` (first axis fastest), evaluated
+        ``chunk`` points at a time (0: the library's default)."""
+        if len(lens) != self.d + self.n:
+            raise _lib.DimensionMismatch(f"a grid needs d + n = {self.d + self.n} axis lengths, got {len(lens)}")
+        arr = (C.c_int64 * max(len(lens), 1))(*[int(v) for v in lens])
+        _lib.check(self.lib.df_flow_logpdf_grid(self.handle, _ptr(axes_buf), arr, C.c_int64(first),
+                                                C.c_int64(count), _ptr(lpbuf), C.c_int64(chunk),
+                                                _stream(self.device)), "logpdf_grid")
+
+    def run_theta_broadcast(self, outbuf, thvec, batch: int):
+        """df_theta_broadcast: the n-vector ``thvec`` into every column of the (n, batch) ``outbuf``."""
+        _lib.check(self.lib.df_theta_broadcast(_ptr(outbuf), _ptr(thvec), C.c_int(int(thvec.numel())),
+                                               C.c_int64(batch), _stream(self.device)), "θ broadcast")
+
     def run_sample(self, xbuf, thbuf, broadcast: bool, batch: int, seed: int, offset: int = 0):
         """df_flow_sample: device N(0, I) draw (Philox, seed/offset) + fused forward!."""
         _lib.check(self.lib.df_flow_sample(self.handle, _ptr(xbuf), _ptr(thbuf), 1 if broadcast else 0,

@@ -224,6 +224,30 @@ int df_flow_sample(df_chain* chain, float* x_out, const float* theta_raw, int th
                    uint64_t seed, uint64_t offset, void* stream);
 int df_random_normal(float* out, int64_t count, uint64_t seed, uint64_t offset, void* stream);
 
+/* ---- grid logpdf ------------------------------------------------------------
+ * logpdf(flow, (x_1, ..., x_d), (θ_1, ..., θ_n)) (src/Flows.jl:287-331; pdf, :348-349, is
+ * its exp): the log-density on the outer product of one vector per dimension, generated on
+ * the device — nothing of the grid's size is built on the host.
+ * axes: DEVICE memory, the d + n axis vectors one after the other (x axes, then raw θ
+ * axes; θ is normalised in the kernel with the chain's bounds).  lens: HOST memory, their
+ * d + n lengths; a θ given as one value is an axis of length 1.
+ * Point p of the P = prod(lens) points has the multi-index (i_1, ..., i_{d+n}) with
+ * p = i_1 + L_1 (i_2 + L_2 (...)): the first axis runs fastest, which is
+ * Iterators.product order and the column-major reshape(..., lens...).  P may exceed
+ * 2^32; the call evaluates the window [first, first + count) and writes `count` values
+ * to logpdf_out (DEVICE), bitwise what df_flow_logpdf gives on the same points.
+ * The window is evaluated `chunk` points at a time (0: 2^20; rounded up to a multiple of
+ * 64, at most 2^24) through a staging buffer of (d + n) * chunk floats that belongs to
+ * the chain and only grows; growing it inside a stream capture is DF_ERR_INVALID.
+ * count == 0 or an empty axis: DF_OK, nothing launched, logpdf_out untouched.
+ * DF_ERR_SHAPE: a negative length, P past int64, a window outside [0, P]. */
+int df_flow_logpdf_grid(df_chain* chain, const float* axes, const int64_t* lens, int64_t first, int64_t count,
+                        float* logpdf_out, int64_t chunk, void* stream);
+
+/* out (n, batch) = the n-vector theta in every column, on the device: the NTuple θ of
+ * logpdf(flow, x, θ::Tuple) (src/Flows.jl:284, collect(θ) broadcast over the points). */
+int df_theta_broadcast(float* out, const float* theta, int n, int64_t batch, void* stream);
+
 /* ---- training ---------------------------------------------------------------
  * train!(flow, data, opt_state; ...) src/Flows.jl:380-445: per batch
  *   grads = Flux.gradient(m -> loss(backward(m, x, θ)...), flow.model)   (:398-411)
