@@ -17,7 +17,8 @@ from .flows import (Flow, MvNormal, logpdf, logpdf_grad, logpdf_grid, nll_partia
                     training_loss, validation_loss)
 from .layers import (Chain, CouplingBlock, CouplingLayer, Dense, FlowElement, NICECouplingLayer,
                      NormalizationLayer, RNVPCouplingLayer, default_net)
-from .train import Adam, TrainState, load_trainables, setup, train_, trainables
+from .train import (Adam, AdamW, ClipGrad, ClipNorm, Descent, OptimiserChain, TrainState, WeightDecay, adjust_,
+                    load_trainables, setup, train_, trainables)
 
 __version__ = "0.1.0"
 

@@ -108,6 +108,19 @@ class df_adam(C.Structure):
     _fields_ = [("eta", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("epsilon", C.c_float)]
 
 
+# df_opt_kind (df_train_create_opt)
+DF_OPT_ADAM = 1
+DF_OPT_DESCENT = 2
+DF_OPT_CLIP_GRAD = 3
+DF_OPT_CLIP_NORM = 4
+DF_OPT_WEIGHT_DECAY = 5
+DF_OPT_MAX_RULES = 8
+
+
+class df_opt_rule(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("p", C.c_float * 4)]
+
+
 _FP = C.POINTER(C.c_float)
 _VP = C.c_void_p
 _I64 = C.c_int64
@@ -147,6 +160,11 @@ SIGNATURES = {
     "df_train_set_params": (C.c_int, [_VP, _FP, _I64]),
     "df_train_set_debug": (C.c_int, [_VP, C.c_int]),
     "df_train_set_theta_input": (C.c_int, [_VP, C.c_int]),
+    "df_train_create_opt": (C.c_int, [C.POINTER(_VP), _VP, C.POINTER(df_opt_rule), C.c_int, C.c_int]),
+    "df_train_adjust": (C.c_int, [_VP, C.c_float]),
+    "df_train_num_tensors": (C.c_int, [_VP, C.POINTER(_I64)]),
+    "df_train_tensor_offsets": (C.c_int, [_VP, C.POINTER(_I64), _I64]),
+    "df_train_grad_norms": (C.c_int, [_VP, _VP, _VP]),
     "df_chain_set_weights": (C.c_int, [_VP, C.POINTER(df_chain_desc)]),
     "df_comm_get_unique_id": (C.c_int, [_VP]),
     "df_comm_init_rank": (C.c_int, [C.POINTER(_VP), C.c_int, _VP, C.c_int, C.c_int]),

@@ -126,6 +126,36 @@ hipError_t launch_repack(float* blob, const int32_t* dst, const int32_t* src, in
 hipError_t launch_repack_split(uint8_t* blob, const int32_t* dst, const int32_t* src, int64_t count,
                                const float* params, hipStream_t st);
 
+// ---- optimiser chains (df_train_create_opt; Optimisers.OptimiserChain) ----
+// The rules of a chain, passed to the kernels by value: kind[r] is a df_opt_kind, p[r] its
+// parameters (df_opt_rule::p).
+constexpr int kOptMaxRules = 8;
+struct OptChain {
+    int32_t n;
+    int32_t kind[kOptMaxRules];
+    float p[kOptMaxRules][4];
+};
+// One 256-thread workgroup of the update kernel: elements [begin, begin + count) of the
+// flat vectors, all of parameter tensor `tensor` (no workgroup spans two tensors).
+struct OptBlock {
+    int32_t begin, count, tensor;
+};
+constexpr int kOptThreads = 256;
+// tensor_sumsq_kernel: the longest chain of additions one element's square goes through.
+// 4 accumulators per thread, each over every 256th quad of the tensor (a tensor has at
+// most 256·256 floats = 16,384 quads: 64 additions), 2 levels to combine the four, and
+// the 8 levels of the workgroup's tree.
+constexpr int kSumsqK = 64 + 2 + 8;
+// out[t] = Σ dx² over tensor t = [toff[t], toff[t+1]) with dx = g after rules [0, n_pre) of
+// the chain (x: the parameters, read by WeightDecay), or its square root (take_sqrt).
+// One workgroup per tensor, fixed summation order, no atomics.
+hipError_t launch_tensor_sumsq(const float* g, const float* x, const int32_t* toff, int n_tensors, const OptChain& ch,
+                               int n_pre, bool take_sqrt, float* out, hipStream_t st);
+// The whole chain per element, then x -= dx; with an Adam in the chain βᵗ .*= β follows
+// (adam_advance_kernel).  sumsq: launch_tensor_sumsq's output for the chain's ClipNorm.
+hipError_t launch_opt_chain(float* x, const float* g, float* m, float* v, float* bt, const float* sumsq,
+                            const OptBlock* blocks, int64_t n_blocks, const OptChain& ch, hipStream_t st);
+
 // ---- per-sample input gradients of logpdf (df_train_logpdf_grad; df_score_impl.h) ----
 // The same sweep as the trainer's with the seed z̄ = -z, j̄ = 1 and no reduction over the
 // batch: score_net_kernel recomputes one conditioner (exact f32, GNet::u), applies the

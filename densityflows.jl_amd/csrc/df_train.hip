@@ -112,6 +112,137 @@ __global__ void adam_advance_kernel(float* bt, float b1, float b2) {
     }
 }
 
+// ---- optimiser chains (Optimisers.OptimiserChain): dx = g through the rules in order ----
+// Every rule is one fixed sequence of correctly rounded Float32 operations, so a Float32
+// restatement matches it: contraction is off in each function below (as the Makefile's
+// -ffp-contract=off has it for the whole unit), and / and sqrtf round correctly.
+
+// clamp(dx, -δ, δ) as Base.clamp: a NaN passes through
+__device__ inline float opt_clip_grad(float dx, float delta) {
+    return dx > delta ? delta : (dx < -delta ? -delta : dx);
+}
+
+__device__ inline float opt_weight_decay(float dx, float x, float lambda) {
+#pragma clang fp contract(off)
+    const float lx = lambda * x;
+    return dx + lx;
+}
+
+// The stateless rules [0, n_pre) that stand before the chain's ClipNorm.
+__device__ inline float opt_pre_rules(const OptChain& ch, int n_pre, float dx, float x) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int r = 0; r < kOptMaxRules; ++r) {
+        if (r >= n_pre) break;
+        const float p0 = ch.p[r][0];
+        switch (ch.kind[r]) {
+            case DF_OPT_CLIP_GRAD: dx = opt_clip_grad(dx, p0); break;
+            case DF_OPT_WEIGHT_DECAY: dx = opt_weight_decay(dx, x, p0); break;
+            case DF_OPT_DESCENT: dx = p0 * dx; break;
+            default: break;
+        }
+    }
+    return dx;
+}
+
+// out[t] = Σ dx² over tensor t (or its square root), one workgroup per tensor.  Element j of
+// the tensor belongs to quad q = j / 4, thread q % 256, accumulator j % 4; each accumulator
+// adds its quads in increasing order, then (a0 + a1) + (a2 + a3), then the workgroup's tree
+// over LDS: the same order on every run and for both load widths (16-byte loads when the
+// tensor starts on a 16-byte boundary, scalar loads otherwise).  The longest chain of
+// additions is kSumsqK (df_train.h).
+__global__ __launch_bounds__(kOptThreads) void tensor_sumsq_kernel(const float* g, const float* x,
+                                                                   const int32_t* toff, OptChain ch, int n_pre,
+                                                                   int need_x, int take_sqrt, float* out) {
+#pragma clang fp contract(off)
+    typedef float v4 __attribute__((ext_vector_type(4)));
+    __shared__ float red[kOptThreads];
+    const int t = blockIdx.x;
+    const int64_t base = toff[t];
+    const int n = toff[t + 1] - toff[t];
+    const float* gt = g + base;
+    const float* xt = x + base;
+    const bool vec = (base & 3) == 0;  // (g and x are hipMalloc allocations)
+    const int nq = (n + 3) / 4;
+    float a[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int q = threadIdx.x; q < nq; q += kOptThreads) {
+        const int j = 4 * q;
+        float d[4], xv[4] = {0.f, 0.f, 0.f, 0.f};
+        if (vec && j + 4 <= n) {
+            const v4 gq = *reinterpret_cast<const v4*>(gt + j);
+            d[0] = gq.x, d[1] = gq.y, d[2] = gq.z, d[3] = gq.w;
+            if (need_x) {
+                const v4 xq = *reinterpret_cast<const v4*>(xt + j);
+                xv[0] = xq.x, xv[1] = xq.y, xv[2] = xq.z, xv[3] = xq.w;
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const bool in = j + c < n;
+                d[c] = in ? gt[j + c] : 0.f;
+                if (need_x) xv[c] = in ? xt[j + c] : 0.f;
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            // (past the tensor's end: dx = 0, which adds +0 and leaves the sum as it is)
+            const float dx = j + c < n ? opt_pre_rules(ch, n_pre, d[c], xv[c]) : 0.f;
+            const float sq = dx * dx;
+            a[c] = a[c] + sq;
+        }
+    }
+    red[threadIdx.x] = (a[0] + a[1]) + (a[2] + a[3]);
+    __syncthreads();
+    for (int s = kOptThreads / 2; s >= 1; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[t] = take_sqrt ? sqrtf(red[0]) : red[0];
+}
+
+// The whole chain on one element, then x -= dx.  Adam is adam_kernel's arithmetic on the
+// incoming dx; ClipNorm's scale comes from sumsq[tensor] (tensor_sumsq_kernel).
+__global__ __launch_bounds__(kOptThreads) void opt_chain_kernel(float* x, const float* g, float* m, float* v,
+                                                                const float* bt, const float* sumsq,
+                                                                const OptBlock* blocks, OptChain ch) {
+#pragma clang fp contract(off)
+    const OptBlock b = blocks[blockIdx.x];
+    if ((int)threadIdx.x >= b.count) return;
+    const int64_t i = (int64_t)b.begin + threadIdx.x;
+    const float xi = x[i];
+    float dx = g[i];
+#pragma unroll
+    for (int r = 0; r < kOptMaxRules; ++r) {
+        if (r >= ch.n) break;
+        const float p0 = ch.p[r][0];
+        switch (ch.kind[r]) {
+            case DF_OPT_CLIP_GRAD: dx = opt_clip_grad(dx, p0); break;
+            case DF_OPT_WEIGHT_DECAY: dx = opt_weight_decay(dx, xi, p0); break;
+            case DF_OPT_DESCENT: dx = p0 * dx; break;
+            case DF_OPT_CLIP_NORM: {
+                const float nrm = sqrtf(sumsq[b.tensor]);
+                if (nrm > p0) {
+                    const float scale = p0 / nrm;
+                    dx = dx * scale;
+                }
+                break;
+            }
+            case DF_OPT_ADAM: {
+                const float b1 = ch.p[r][1], b2 = ch.p[r][2], eps = ch.p[r][3];
+                const float bt1 = bt[0], bt2 = bt[1];
+                const float mi = b1 * m[i] + (1.f - b1) * dx;
+                const float vi = b2 * v[i] + (1.f - b2) * (dx * dx);
+                m[i] = mi;
+                v[i] = vi;
+                dx = mi / (1.f - bt1) / (sqrtf(vi / (1.f - bt2)) + eps) * p0;
+                break;
+            }
+            default: break;
+        }
+    }
+    x[i] = xi - dx;
+}
+
 __global__ void repack_kernel(float* blob, const int32_t* dst, const int32_t* src, int64_t count,
                               const float* params) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -209,6 +340,27 @@ hipError_t launch_adam(float* x, const float* g, float* m, float* v, int64_t cou
         hipLaunchKernelGGL(adam_kernel, dim3(blocks_for(count, 256)), dim3(256), 0, st, x, g, m, v, count, eta, b1, b2,
                            eps, static_cast<const float*>(bt));
     hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(64), 0, st, bt, b1, b2);
+    return hipGetLastError();
+}
+
+hipError_t launch_tensor_sumsq(const float* g, const float* x, const int32_t* toff, int n_tensors, const OptChain& ch,
+                               int n_pre, bool take_sqrt, float* out, hipStream_t st) {
+    if (n_tensors <= 0) return hipSuccess;
+    int need_x = 0;
+    for (int r = 0; r < n_pre; ++r) need_x |= ch.kind[r] == DF_OPT_WEIGHT_DECAY;
+    hipLaunchKernelGGL(tensor_sumsq_kernel, dim3((unsigned)n_tensors), dim3(kOptThreads), 0, st, g, x, toff, ch, n_pre,
+                       need_x, take_sqrt ? 1 : 0, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_opt_chain(float* x, const float* g, float* m, float* v, float* bt, const float* sumsq,
+                            const OptBlock* blocks, int64_t n_blocks, const OptChain& ch, hipStream_t st) {
+    if (n_blocks > 0)
+        hipLaunchKernelGGL(opt_chain_kernel, dim3((unsigned)n_blocks), dim3(kOptThreads), 0, st, x, g, m, v,
+                           static_cast<const float*>(bt), sumsq, blocks, ch);
+    for (int r = 0; r < ch.n; ++r)
+        if (ch.kind[r] == DF_OPT_ADAM)
+            hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(64), 0, st, bt, ch.p[r][1], ch.p[r][2]);
     return hipGetLastError();
 }
 

@@ -166,6 +166,19 @@ struct df_train {
     bool fmode = false;
     int sweep_req = DF_SWEEP_AUTO;   // df_train_create_ex: the requested form (df_sweep_form)
     bool separate = false;           // DF_SWEEP_SEPARATE: unmerged dW / front launches
+    // The parameter tensors (one Dense weight or bias each) as slices of the flat vectors:
+    // tensor k is [toff[k], toff[k+1]).  On the device (d_toff) once a kernel needs them.
+    std::vector<int32_t> toff;
+    DevBuf d_toff;
+    // Optimiser chain (df_train_create_opt).  A chain that is exactly [Adam] is not one:
+    // chain_mode stays false and df_train_apply launches adam_kernel with `opt`.
+    bool chain_mode = false;
+    OptChain och{};
+    int och_clip = -1;               // index of the chain's ClipNorm (-1: none): the rules before it
+                                     //   run inside the Σ dx² kernel too
+    int och_eta = -1;                // the rule df_train_adjust sets η of: the Adam, else the first Descent
+    DevBuf d_sumsq, d_oblocks;       // float [tensors] Σ dx²; OptBlock [n_oblocks] of the update kernel
+    int64_t n_oblocks = 0;
 };
 
 namespace {
@@ -955,6 +968,97 @@ int lsweep(df_train* t, const float* x, const float* theta, int64_t batch, float
     return s.rc;
 }
 
+// The rules of df_train_create_opt, validated (include/densityflows_hip.h: limits and values)
+// into the kernels' OptChain.  clip: index of the ClipNorm; eta_rule: the rule
+// df_train_adjust writes; adam: the chain's Adam (its β seed and advance βᵗ).
+int check_rules(const df_opt_rule* rules, int n_rules, OptChain& och, int& clip, int& eta_rule, df_adam& adam) {
+    if (!rules && n_rules > 0) return set_err(DF_ERR_INVALID, "null pointer");
+    if (n_rules < 1) return set_err(DF_ERR_UNSUPPORTED, "OptimiserChain: no rule (a chain needs an Adam or a Descent)");
+    if (n_rules > kOptMaxRules) return set_err(DF_ERR_UNSUPPORTED, "OptimiserChain: more than 8 rules");
+    int i_adam = -1, i_descent = -1;
+    clip = -1;
+    och = OptChain{};
+    och.n = n_rules;
+    for (int r = 0; r < n_rules; ++r) {
+        const float* p = rules[r].p;
+        och.kind[r] = rules[r].kind;
+        switch (rules[r].kind) {
+            case DF_OPT_ADAM:
+                if (i_adam >= 0) return set_err(DF_ERR_UNSUPPORTED, "OptimiserChain: more than one Adam");
+                if (!(p[0] >= 0.f) || !(p[1] >= 0.f && p[1] < 1.f) || !(p[2] >= 0.f && p[2] < 1.f) || !(p[3] >= 0.f))
+                    return set_err(DF_ERR_INVALID, "invalid Adam hyper-parameters");
+                i_adam = r;
+                adam = df_adam{p[0], p[1], p[2], p[3]};
+                for (int k = 0; k < 4; ++k) och.p[r][k] = p[k];
+                break;
+            case DF_OPT_DESCENT:
+                if (!(p[0] >= 0.f)) return set_err(DF_ERR_INVALID, "invalid Descent learning rate (η >= 0)");
+                if (i_descent < 0) i_descent = r;
+                och.p[r][0] = p[0];
+                break;
+            case DF_OPT_CLIP_GRAD:
+                if (!(p[0] > 0.f)) return set_err(DF_ERR_INVALID, "invalid ClipGrad bound (δ > 0)");
+                och.p[r][0] = p[0];
+                break;
+            case DF_OPT_CLIP_NORM:
+                if (clip >= 0) return set_err(DF_ERR_UNSUPPORTED, "OptimiserChain: more than one ClipNorm");
+                if (i_adam >= 0)
+                    return set_err(DF_ERR_UNSUPPORTED, "OptimiserChain: ClipNorm after Adam (it stands before it)");
+                if (!(p[0] > 0.f)) return set_err(DF_ERR_INVALID, "invalid ClipNorm bound (ω > 0)");
+                clip = r;
+                och.p[r][0] = p[0];
+                break;
+            case DF_OPT_WEIGHT_DECAY:
+                if (!(p[0] >= 0.f)) return set_err(DF_ERR_INVALID, "invalid WeightDecay factor (λ >= 0)");
+                och.p[r][0] = p[0];
+                break;
+            default:
+                return set_err(DF_ERR_UNSUPPORTED, "OptimiserChain: unknown rule (df_opt_kind)");
+        }
+    }
+    if (i_adam < 0 && i_descent < 0)
+        return set_err(DF_ERR_UNSUPPORTED, "OptimiserChain: no terminal rule (a chain needs an Adam or a Descent)");
+    eta_rule = i_adam >= 0 ? i_adam : i_descent;
+    return DF_OK;
+}
+
+// Every Dense weight and bias as a slice of the flat trainables, in increasing order.
+// False unless they tile [0, P) exactly.
+bool tensor_table(const Plan& P, std::vector<int32_t>& toff) {
+    std::vector<std::pair<int32_t, int32_t>> sl;  // (offset, count)
+    for (const DevDense& D : P.denses) {
+        sl.push_back({D.w_off, D.in_dim * D.n_out});
+        if (D.b_off >= 0) sl.push_back({D.b_off, D.n_out});
+    }
+    std::sort(sl.begin(), sl.end());
+    toff.assign(1, 0);
+    for (const auto& s : sl) {
+        if (s.first != toff.back() || s.second <= 0) return false;
+        toff.push_back(s.first + s.second);
+    }
+    return (int64_t)toff.back() == (int64_t)P.trainables.size();
+}
+
+int ensure_toff(df_train* t) { return t->d_toff.get() ? DF_OK : upload(t->toff, t->d_toff); }
+
+// Device state of an optimiser chain: the tensor offsets, Σ dx² per tensor and the update
+// kernel's workgroup → tensor table (built once: no workgroup spans two tensors).
+int setup_chain(df_train* t) {
+    std::vector<OptBlock> blocks;
+    const int nt = (int)t->toff.size() - 1;
+    for (int k = 0; k < nt; ++k)
+        for (int32_t b = t->toff[k]; b < t->toff[k + 1]; b += kOptThreads)
+            blocks.push_back({b, std::min<int32_t>(kOptThreads, t->toff[k + 1] - b), k});
+    t->n_oblocks = (int64_t)blocks.size();
+    int rc = ensure_toff(t);
+    if (rc == DF_OK) rc = upload(blocks, t->d_oblocks);
+    if (rc != DF_OK) return rc;
+    const size_t sb = sizeof(float) * (size_t)std::max(nt, 4);
+    if (t->d_sumsq.alloc(sb) != hipSuccess) return set_err(DF_ERR_NOMEM, "hipMalloc failed (optimiser chain)");
+    if (hipMemset(t->d_sumsq.get(), 0, sb) != hipSuccess) return set_err(DF_ERR_HIP, "hipMemset(optimiser chain)");
+    return DF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -973,8 +1077,19 @@ int df_train_create(df_train** out, df_chain* c, const df_adam* opt) {
 }
 
 int df_train_create_ex(df_train** out, df_chain* c, const df_adam* opt, int sweep) {
+    const df_adam a = opt ? *opt : df_adam{1e-3f, 0.9f, 0.999f, 1e-8f};
+    const df_opt_rule rule{DF_OPT_ADAM, {a.eta, a.beta1, a.beta2, a.epsilon}};
+    return df_train_create_opt(out, c, &rule, 1, sweep);
+}
+
+int df_train_create_opt(df_train** out, df_chain* c, const df_opt_rule* rules, int n_rules, int sweep) {
     if (!out || !c) return set_err(DF_ERR_INVALID, "null pointer");
     *out = nullptr;
+    OptChain och{};
+    int clip = -1, eta_rule = -1;
+    df_adam adam{1e-3f, 0.9f, 0.999f, 1e-8f};
+    int rc0 = check_rules(rules, n_rules, och, clip, eta_rule, adam);
+    if (rc0 != DF_OK) return rc0;
     const int form = sweep & ~DF_SWEEP_SEPARATE;
     if (form < DF_SWEEP_AUTO || form > DF_SWEEP_LAYERWISE || (sweep & ~(DF_SWEEP_SEPARATE | 7)))
         return set_err(DF_ERR_INVALID, "unknown sweep form");
@@ -986,14 +1101,17 @@ int df_train_create_ex(df_train** out, df_chain* c, const df_adam* opt, int swee
     t->sweep_req = form;
     t->separate = (sweep & DF_SWEEP_SEPARATE) != 0;
     if (const char* v = std::getenv("DF_SCORE_PER_NET")) t->score_per_net = v[0] == '1';
-    t->opt = opt ? *opt : df_adam{1e-3f, 0.9f, 0.999f, 1e-8f};
-    if (!(t->opt.eta >= 0.f) || !(t->opt.beta1 >= 0.f && t->opt.beta1 < 1.f) ||
-        !(t->opt.beta2 >= 0.f && t->opt.beta2 < 1.f) || !(t->opt.epsilon >= 0.f)) {
-        delete t;
-        return set_err(DF_ERR_INVALID, "invalid Adam hyper-parameters");
-    }
+    t->opt = adam;
+    t->och = och;
+    t->och_clip = clip;
+    t->och_eta = eta_rule;
+    t->chain_mode = !(och.n == 1 && och.kind[0] == DF_OPT_ADAM);
     const Plan& P = c->plan;
     t->P = (int64_t)P.trainables.size();
+    if (!tensor_table(P, t->toff)) {
+        delete t;
+        return set_err(DF_ERR_INVALID, "internal: the Dense tensors do not tile the flat trainables");
+    }
     t->amode = P.relu_only ? trn::AM_RELU : trn::AM_Y;
     for (const DevDense& D : P.denses)
         if (act_needs_pre(D.act) && !P.relu_only) t->amode = trn::AM_PRE;
@@ -1128,6 +1246,12 @@ int df_train_create_ex(df_train** out, df_chain* c, const df_adam* opt, int swee
                      hipMemset(t->d_grad.get(), 0, sizeof(float) * t->P) != hipSuccess)) {
         df_train_destroy(t);
         return set_err(DF_ERR_HIP, "initialising the training state failed");
+    }
+    // (after every allocation a plain-Adam trainer makes: theirs keep their places)
+    if (t->chain_mode && (rc = setup_chain(t)) != DF_OK) {
+        std::string m = last_error();
+        df_train_destroy(t);
+        return set_err(rc, m);
     }
     *out = t;
     return DF_OK;
@@ -1381,9 +1505,24 @@ int df_train_apply(df_train* t, void* stream) {
             return set_err(DF_ERR_NONFINITE, msg);
         }
     }
-    hipError_t e = launch_adam(t->d_params.as<float>(), t->d_grad.as<const float>(), t->d_m.as<float>(),
-                               t->d_v.as<float>(), t->P, t->opt.eta, t->opt.beta1, t->opt.beta2, t->opt.epsilon,
-                               t->d_bt.as<float>(), st);
+    hipError_t e = hipSuccess;
+    if (t->chain_mode) {
+        // Σ dx² per tensor for the ClipNorm (the rules before it applied on the fly), then
+        // the whole chain per element in one kernel
+        if (t->och_clip >= 0) {
+            e = launch_tensor_sumsq(t->d_grad.as<const float>(), t->d_params.as<const float>(),
+                                    t->d_toff.as<const int32_t>(), (int)t->toff.size() - 1, t->och, t->och_clip, false,
+                                    t->d_sumsq.as<float>(), st);
+            if (e != hipSuccess) return hip_err(e, "tensor norm kernel launch");
+        }
+        e = launch_opt_chain(t->d_params.as<float>(), t->d_grad.as<const float>(), t->d_m.as<float>(),
+                             t->d_v.as<float>(), t->d_bt.as<float>(), t->d_sumsq.as<const float>(),
+                             t->d_oblocks.as<const OptBlock>(), t->n_oblocks, t->och, st);
+        if (e != hipSuccess) return hip_err(e, "optimiser chain kernel launch");
+        return repack(t, st);
+    }
+    e = launch_adam(t->d_params.as<float>(), t->d_grad.as<const float>(), t->d_m.as<float>(), t->d_v.as<float>(),
+                    t->P, t->opt.eta, t->opt.beta1, t->opt.beta2, t->opt.epsilon, t->d_bt.as<float>(), st);
     if (e != hipSuccess) return hip_err(e, "Adam kernel launch");
     return repack(t, st);
 }
@@ -1508,6 +1647,44 @@ int df_train_set_params(df_train* t, const float* host_in, int64_t count) {
     if (rc != DF_OK) return rc;
     e = hipDeviceSynchronize();
     return e == hipSuccess ? DF_OK : hip_err(e, "repack");
+}
+
+int df_train_adjust(df_train* t, float eta) {
+    if (!t) return set_err(DF_ERR_INVALID, "null trainer");
+    if (!(eta >= 0.f)) return set_err(DF_ERR_INVALID, "invalid learning rate (η >= 0)");
+    t->och.p[t->och_eta][0] = eta;
+    if (t->och.kind[t->och_eta] == DF_OPT_ADAM) t->opt.eta = eta;
+    t->cap_gen++;  // η is a kernel argument of the captured steps: they are re-captured
+    return DF_OK;
+}
+
+int df_train_num_tensors(const df_train* t, int64_t* count) {
+    if (!t || !count) return set_err(DF_ERR_INVALID, "null pointer");
+    *count = (int64_t)t->toff.size() - 1;
+    return DF_OK;
+}
+
+int df_train_tensor_offsets(const df_train* t, int64_t* offsets_out, int64_t count_plus_1) {
+    if (!t || !offsets_out) return set_err(DF_ERR_INVALID, "null pointer");
+    if (count_plus_1 != (int64_t)t->toff.size())
+        return set_err(DF_ERR_SHAPE, "count_plus_1 must equal df_train_num_tensors + 1");
+    for (size_t k = 0; k < t->toff.size(); ++k) offsets_out[k] = t->toff[k];
+    return DF_OK;
+}
+
+int df_train_grad_norms(df_train* t, float* out_dev, void* stream) {
+    if (!t) return set_err(DF_ERR_INVALID, "null trainer");
+    const int nt = (int)t->toff.size() - 1;
+    if (nt == 0) return DF_OK;
+    if (!out_dev) return set_err(DF_ERR_INVALID, "null output array");
+    DeviceGuard gd(t->c->device);
+    if (!gd.ok) return set_err(DF_ERR_HIP, "hipSetDevice failed");
+    const int rc = ensure_toff(t);
+    if (rc != DF_OK) return rc;
+    const hipError_t e =
+        launch_tensor_sumsq(t->d_grad.as<const float>(), t->d_params.as<const float>(), t->d_toff.as<const int32_t>(),
+                            nt, t->och, 0, true, out_dev, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? DF_OK : hip_err(e, "tensor norm kernel launch");
 }
 
 }  // extern "C"

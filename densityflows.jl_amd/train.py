@@ -7,7 +7,9 @@ s/t conditioners and back-propagates through the coupling pullbacks
 src/affine/NICE.jl:84-113) and the Dense chains on MFMA, gradients are
 reduced in a fixed order, then Adam updates the flat parameters and the
 packed weights are regathered, so the Flow's forward / logpdf / sample see
-the new parameters immediately.
+the new parameters immediately.  Instead of a bare ``Adam`` the optimiser may be an
+``OptimiserChain`` of ``ClipGrad`` / ``ClipNorm`` / ``WeightDecay`` / ``Adam`` / ``Descent``
+(``df_train_create_opt``): the whole chain then runs on the device inside ``apply``.
 
 Data parallelism (one process per GPU): :func:`train_` with a
 ``torch.distributed`` process group shards every batch over the ranks,
@@ -26,7 +28,8 @@ from . import _lib
 from .hip import HIPChain, _ptr, _stream, as_julia_device, flatten_elements
 from .layers import NormalizationLayer, RNVPCouplingLayer
 
-__all__ = ["Adam", "setup", "TrainState", "HIPTrainer", "train_", "trainables", "load_trainables"]
+__all__ = ["Adam", "Descent", "ClipGrad", "ClipNorm", "WeightDecay", "OptimiserChain", "AdamW", "setup", "adjust_",
+           "TrainState", "HIPTrainer", "train_", "trainables", "load_trainables"]
 
 
 class Adam:
@@ -39,6 +42,121 @@ class Adam:
 
     def __repr__(self):
         return f"Adam(eta={self.eta}, beta={self.beta}, epsilon={self.epsilon})"
+
+
+class Descent:
+    """``Optimisers.Descent(η = 1f-1)``: ``dx = η·dx``."""
+
+    def __init__(self, eta: float = 0.1):
+        self.eta = float(eta)
+
+    def __repr__(self):
+        return f"Descent(eta={self.eta})"
+
+
+class ClipGrad:
+    """``Optimisers.ClipGrad(δ = 10)``: ``dx = clamp(dx, -δ, δ)`` elementwise."""
+
+    def __init__(self, delta: float = 10.0):
+        self.delta = float(delta)
+
+    def __repr__(self):
+        return f"ClipGrad(delta={self.delta})"
+
+
+class ClipNorm:
+    """``Optimisers.ClipNorm(ω = 10)`` with p = 2, per parameter tensor (one Dense weight or
+    bias): ``nrm = sqrt(Σ dx²)``; where ``nrm > ω``, ``dx = dx·(ω / nrm)``."""
+
+    def __init__(self, omega: float = 10.0):
+        self.omega = float(omega)
+
+    def __repr__(self):
+        return f"ClipNorm(omega={self.omega})"
+
+
+class WeightDecay:
+    """``Optimisers.WeightDecay(λ = 5f-4)``: ``dx = dx + λ·x``.  Before ``Adam`` in a chain
+    it is L2 regularisation, after it decoupled decay."""
+
+    def __init__(self, lam: float = 5e-4):
+        self.lam = float(lam)
+
+    def __repr__(self):
+        return f"WeightDecay(lam={self.lam})"
+
+
+class OptimiserChain:
+    """``Optimisers.OptimiserChain(rules...)``: every rule in order maps ``dx ← rule(x, dx)``
+    from ``dx = ∇``, then ``x ← x - dx``.  Nested chains are flattened.  The device runs
+    chains of at most 8 rules with at most one ``Adam``, at most one ``ClipNorm`` (before
+    the ``Adam``) and at least one of ``Adam`` / ``Descent``."""
+
+    def __init__(self, *rules):
+        self.rules = []
+        for r in rules:
+            self.rules += r.rules if isinstance(r, OptimiserChain) else [r]
+
+    def __repr__(self):
+        return "OptimiserChain(" + ", ".join(repr(r) for r in self.rules) + ")"
+
+
+def AdamW(eta: float = 1e-3, beta=(0.9, 0.999), lam: float = 0.0, epsilon: float = 1e-8) -> OptimiserChain:
+    """``Optimisers.AdamW(η, β, λ, ϵ)``: sugar for
+    ``OptimiserChain(Adam(η, β, ϵ), WeightDecay(λ))`` — decoupled decay, ``x -= η·û + λ·x``."""
+    return OptimiserChain(Adam(eta, beta, epsilon), WeightDecay(lam))
+
+
+MAX_RULES = _lib.DF_OPT_MAX_RULES
+# the longest chain of Float32 additions behind one tensor's Σ dx² (kSumsqK, csrc/df_train.h):
+# grad_norms() is within (GRAD_NORM_K + 3)·2⁻²⁴ of the exact norm, relatively
+GRAD_NORM_K = 74
+
+
+def chain_rules(opt) -> list:
+    """The rules of ``opt`` (a rule or an OptimiserChain) as ``(df_opt_kind, (p0..p3))``,
+    checked against the device's limits before the library is touched: bad values raise
+    ``ArgumentError`` (DF_ERR_INVALID), a structure outside the limits ``UnsupportedError``
+    (DF_ERR_UNSUPPORTED).  The message names the rule."""
+    rules = opt.rules if isinstance(opt, OptimiserChain) else [opt]
+    out = []
+    bad = lambda *v: any(not (x >= 0.0) for x in v)  # negative or NaN
+    for r in rules:
+        if isinstance(r, Adam):
+            if bad(r.eta, r.epsilon, *r.beta) or r.beta[0] >= 1.0 or r.beta[1] >= 1.0:
+                raise _lib.ArgumentError(f"invalid Adam hyper-parameters: {r!r}")
+            out.append((_lib.DF_OPT_ADAM, (r.eta, r.beta[0], r.beta[1], r.epsilon)))
+        elif isinstance(r, Descent):
+            if bad(r.eta):
+                raise _lib.ArgumentError(f"invalid Descent learning rate (η >= 0): {r!r}")
+            out.append((_lib.DF_OPT_DESCENT, (r.eta, 0.0, 0.0, 0.0)))
+        elif isinstance(r, ClipGrad):
+            if not r.delta > 0.0:
+                raise _lib.ArgumentError(f"invalid ClipGrad bound (δ > 0): {r!r}")
+            out.append((_lib.DF_OPT_CLIP_GRAD, (r.delta, 0.0, 0.0, 0.0)))
+        elif isinstance(r, ClipNorm):
+            if not r.omega > 0.0:
+                raise _lib.ArgumentError(f"invalid ClipNorm bound (ω > 0): {r!r}")
+            out.append((_lib.DF_OPT_CLIP_NORM, (r.omega, 0.0, 0.0, 0.0)))
+        elif isinstance(r, WeightDecay):
+            if bad(r.lam):
+                raise _lib.ArgumentError(f"invalid WeightDecay factor (λ >= 0): {r!r}")
+            out.append((_lib.DF_OPT_WEIGHT_DECAY, (r.lam, 0.0, 0.0, 0.0)))
+        else:
+            raise _lib.UnsupportedError(f"OptimiserChain: the device has no rule {r!r}")
+    kinds = [k for k, _ in out]
+    if len(out) > MAX_RULES:
+        raise _lib.UnsupportedError(f"OptimiserChain: more than {MAX_RULES} rules")
+    if kinds.count(_lib.DF_OPT_ADAM) > 1:
+        raise _lib.UnsupportedError("OptimiserChain: more than one Adam")
+    if kinds.count(_lib.DF_OPT_CLIP_NORM) > 1:
+        raise _lib.UnsupportedError("OptimiserChain: more than one ClipNorm")
+    if _lib.DF_OPT_ADAM not in kinds and _lib.DF_OPT_DESCENT not in kinds:
+        raise _lib.UnsupportedError("OptimiserChain: no terminal rule (a chain needs an Adam or a Descent)")
+    if (_lib.DF_OPT_CLIP_NORM in kinds and _lib.DF_OPT_ADAM in kinds
+            and kinds.index(_lib.DF_OPT_CLIP_NORM) > kinds.index(_lib.DF_OPT_ADAM)):
+        raise _lib.UnsupportedError("OptimiserChain: ClipNorm after Adam (it stands before it)")
+    return out
 
 
 class _DeviceArray:
@@ -59,19 +177,27 @@ SWEEP_NAMES = {SWEEP_FUSED: "fused", SWEEP_H0FREE: "h0free", SWEEP_KEPT: "kept",
 
 
 class HIPTrainer:
-    """A ``df_train`` handle bound to a compiled chain (one device).  ``sweep``: a
+    """A ``df_train`` handle bound to a compiled chain (one device).  ``opt``: an ``Adam``
+    (df_train_create_ex, the plain Adam kernels) or any other rule / ``OptimiserChain``
+    (df_train_create_opt; ``apply`` then runs the whole chain on the device).  ``sweep``: a
     df_sweep_form to request (default: the library picks, SWEEP_AUTO)."""
 
-    def __init__(self, chain: HIPChain, opt: Adam, sweep: int | None = None):
+    def __init__(self, chain: HIPChain, opt, sweep: int | None = None):
         self.chain = chain  # keeps the df_chain alive for this handle's lifetime
         self.lib = chain.lib
         self.opt = opt
         h = C.c_void_p()
-        a = _lib.df_adam(opt.eta, opt.beta[0], opt.beta[1], opt.epsilon)
         sweep = DEFAULT_SWEEP if sweep is None else sweep
-        if sweep == SWEEP_AUTO and not hasattr(self.lib, "df_train_create_ex"):  # a pre-ABI-5 build (A/B runs)
+        if not isinstance(opt, Adam):  # any other rule or an OptimiserChain: df_train_create_opt
+            rules = chain_rules(opt)
+            arr = (_lib.df_opt_rule * len(rules))(*[_lib.df_opt_rule(k, p) for k, p in rules])
+            _lib.check(self.lib.df_train_create_opt(C.byref(h), chain.handle, arr, len(rules), int(sweep)),
+                       "df_train_create_opt")
+        elif sweep == SWEEP_AUTO and not hasattr(self.lib, "df_train_create_ex"):  # a pre-ABI-5 build (A/B runs)
+            a = _lib.df_adam(opt.eta, opt.beta[0], opt.beta[1], opt.epsilon)
             _lib.check(self.lib.df_train_create(C.byref(h), chain.handle, C.byref(a)), "df_train_create")
         else:
+            a = _lib.df_adam(opt.eta, opt.beta[0], opt.beta[1], opt.epsilon)
             _lib.check(self.lib.df_train_create_ex(C.byref(h), chain.handle, C.byref(a), int(sweep)),
                        "df_train_create_ex")
         self.handle = h
@@ -130,6 +256,34 @@ class HIPTrainer:
         _lib.check(self.lib.df_train_step_graph(self.handle, _ptr(xbuf), _ptr(thbuf), C.c_int64(batch),
                                                 C.c_int64(n_total), _ptr(lpsum), _stream(self.device)),
                    "df_train_step_graph")
+
+    def adjust(self, eta: float) -> None:
+        """``Optimisers.adjust!(state, η)`` (df_train_adjust): a new η for the chain's Adam, or
+        without one its first Descent.  The moments and βᵗ are kept; captured steps are
+        re-captured."""
+        _lib.check(self.lib.df_train_adjust(self.handle, C.c_float(eta)), "df_train_adjust")
+        self.eta = float(eta)
+
+    def tensor_offsets(self) -> np.ndarray:
+        """The parameter tensors (one Dense weight or bias each) as slices of the flat vectors:
+        count + 1 int64 offsets (df_train_tensor_offsets).  ClipNorm's norms are per tensor."""
+        n = C.c_int64()
+        _lib.check(self.lib.df_train_num_tensors(self.handle, C.byref(n)), "df_train_num_tensors")
+        out = np.empty(int(n.value) + 1, dtype=np.int64)
+        _lib.check(self.lib.df_train_tensor_offsets(self.handle, out.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                    C.c_int64(out.shape[0])), "df_train_tensor_offsets")
+        return out
+
+    def grad_norms(self):
+        """Per-tensor 2-norms of the gradient buffer as it stands (df_train_grad_norms): a
+        float32 device tensor, one entry per tensor of ``tensor_offsets()``."""
+        import torch
+
+        n = C.c_int64()
+        _lib.check(self.lib.df_train_num_tensors(self.handle, C.byref(n)), "df_train_num_tensors")
+        out = torch.empty(int(n.value), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.df_train_grad_norms(self.handle, _ptr(out), _stream(self.device)), "df_train_grad_norms")
+        return out
 
     def sweep(self) -> int:
         """The reverse-sweep form this trainer runs (df_train_sweep: SWEEP_* | SWEEP_SEPARATE)."""
@@ -211,7 +365,7 @@ def load_trainables(model, flat) -> None:
 class TrainState:
     """``Optimisers.setup(opt, flow.model)``: the device-resident optimiser state."""
 
-    def __init__(self, flow, opt: Adam, device=None):
+    def __init__(self, flow, opt, device=None):
         self.flow = flow
         self.opt = opt
         self.trainer = HIPTrainer(flow.hip(device), opt)
@@ -221,8 +375,14 @@ class TrainState:
         load_trainables(self.flow.model, self.trainer.get_params())
 
 
-def setup(opt: Adam, flow, device=None) -> TrainState:
+def setup(opt, flow, device=None) -> TrainState:
+    """``Optimisers.setup(opt, flow.model)``; ``opt``: a rule or an ``OptimiserChain``."""
     return TrainState(flow, opt, device)
+
+
+def adjust_(state: TrainState, eta: float) -> None:
+    """``Optimisers.adjust!(state, η)``: a new learning rate, the moments kept (HIPTrainer.adjust)."""
+    state.trainer.adjust(eta)
 
 
 def _dist():

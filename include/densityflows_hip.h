@@ -372,7 +372,8 @@ int df_train_logpdf_grad(df_train* t, const float* x, const float* theta, float*
 /* Device pointer of the flat gradient (count floats); all-reduce it here
  * for multi-GPU data parallelism. */
 int df_train_grad_ptr(df_train* t, float** grad_dev);
-/* One Adam step with the current gradient; repacks the chain's weights. */
+/* One optimiser step (Adam, or the chain of df_train_create_opt) with the current
+ * gradient; repacks the chain's weights. */
 int df_train_apply(df_train* t, void* stream);
 /* df_train_gradient (n_total = batch) followed by df_train_apply. */
 int df_train_step(df_train* t, const float* x, const float* theta_raw, int64_t batch, double* logpdf_sum,
@@ -398,6 +399,52 @@ int df_train_set_debug(df_train* t, int on);
 /* Copy the current trainables to / from host memory (count floats). */
 int df_train_get_params(df_train* t, float* host_out, int64_t count);
 int df_train_set_params(df_train* t, const float* host_in, int64_t count);
+
+/* ---- optimiser chains: Optimisers.OptimiserChain on the device (additive to ABI 5) ----
+ * A chain is an ordered list of 1..DF_OPT_MAX_RULES rules.  For every parameter tensor
+ * (one Dense weight or one Dense bias: the leaves Optimisers.setup sees), with x the
+ * parameters before the step and dx = the flat gradient (df_train_gradient, or what the
+ * all-reduce left), each rule in order maps dx ← rule(x, dx), then x ← x - dx.  Float32:
+ *   DF_OPT_ADAM          p = {η, β1, β2, ϵ}   Optimisers.Adam on the incoming dx: m, v updated,
+ *                                             dx = m / (1-β1ᵗ) / (sqrt(v / (1-β2ᵗ)) + ϵ) · η
+ *   DF_OPT_DESCENT       p = {η}              dx = η · dx
+ *   DF_OPT_CLIP_GRAD     p = {δ}              dx = clamp(dx, -δ, δ)
+ *   DF_OPT_CLIP_NORM     p = {ω}              nrm = sqrt(Σ dx²) over the tensor (p = 2);
+ *                                             nrm > ω: dx = dx · (ω / nrm), else dx as it is
+ *                                             (so also for nrm == 0 and a NaN nrm)
+ *   DF_OPT_WEIGHT_DECAY  p = {λ}              dx = dx + λ · x
+ * WeightDecay before Adam is L2 regularisation, after it decoupled decay (AdamW).
+ * Limits: at most one Adam, at most one ClipNorm and at least one of Adam / Descent per
+ * chain; a ClipNorm stands before the chain's Adam.  Outside them: DF_ERR_UNSUPPORTED.
+ * Bad values (δ, ω <= 0, λ < 0, η < 0, β outside [0, 1), ϵ < 0, any NaN): DF_ERR_INVALID.
+ * The message names the rule. */
+#define DF_OPT_MAX_RULES 8
+typedef enum df_opt_kind {
+    DF_OPT_ADAM = 1,
+    DF_OPT_DESCENT = 2,
+    DF_OPT_CLIP_GRAD = 3,
+    DF_OPT_CLIP_NORM = 4,
+    DF_OPT_WEIGHT_DECAY = 5
+} df_opt_kind;
+typedef struct df_opt_rule {
+    int32_t kind;
+    float p[4];
+} df_opt_rule;
+/* Optimisers.setup(OptimiserChain(rules...), flow.model), with a sweep form as
+ * df_train_create_ex.  df_train_create / df_train_create_ex are the one-rule chain [Adam];
+ * a chain that is exactly [Adam] runs their kernels. */
+int df_train_create_opt(df_train** out, df_chain* chain, const df_opt_rule* rules, int n_rules, int sweep);
+/* Optimisers.adjust!(state, η): sets η of the chain's Adam, or without one of its first
+ * Descent; m, v and βᵗ are kept.  Captured df_train_step_graph steps are re-captured. */
+int df_train_adjust(df_train* t, float eta);
+/* The parameter tensors as slices of the flat vectors: `count` tensors, and count + 1
+ * offsets (host memory; tensor k is [offsets[k], offsets[k+1]), offsets[count] =
+ * df_train_num_params).  ClipNorm's norms are taken over these. */
+int df_train_num_tensors(const df_train* t, int64_t* count);
+int df_train_tensor_offsets(const df_train* t, int64_t* offsets_out, int64_t count_plus_1);
+/* Per-tensor 2-norms of the gradient buffer as it stands (df_train_num_tensors device
+ * floats).  Stream-ordered, changes no state, bitwise reproducible (fixed-order sums). */
+int df_train_grad_norms(df_train* t, float* out_dev, void* stream);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI ------------------------
  * The batch is sharded into contiguous sample blocks (samples are independent
