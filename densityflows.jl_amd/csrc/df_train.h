@@ -156,6 +156,19 @@ hipError_t launch_tensor_sumsq(const float* g, const float* x, const int32_t* to
 hipError_t launch_opt_chain(float* x, const float* g, float* m, float* v, float* bt, const float* sumsq,
                             const OptBlock* blocks, int64_t n_blocks, const OptChain& ch, hipStream_t st);
 
+// ---- device-resident epochs (df_batch_gather, df_train_epoch; df_epoch.hip) ----
+// x_out[j] / th_out[j] (d / n floats per sample) = row order[pos + j] of the set (order ==
+// nullptr: pos + j) for j < count, pos = first + *cursor · batchsize (cursor == nullptr:
+// first).  A position or an index outside [0, n_samples) reads row 0.  th_out or th_set
+// nullptr: x alone.
+hipError_t launch_batch_gather(float* x_out, float* th_out, const float* x_set, const float* th_set, int d, int n,
+                               int64_t n_samples, const int32_t* order, int64_t first, const int64_t* cursor,
+                               int64_t batchsize, int64_t count, hipStream_t st);
+// *bad (device int) = how many of order[0, n_samples) lie outside [0, n_samples)
+hipError_t launch_order_range(const int32_t* order, int64_t n_samples, int* bad, hipStream_t st);
+// step_lp[*cursor] = *lp (step_lp may be nullptr), then *cursor += 1: one thread
+hipError_t launch_cursor_advance(int64_t* cursor, const double* lp, double* step_lp, hipStream_t st);
+
 // ---- per-sample input gradients of logpdf (df_train_logpdf_grad; df_score_impl.h) ----
 // The same sweep as the trainer's with the seed z̄ = -z, j̄ = 1 and no reduction over the
 // batch: score_net_kernel recomputes one conditioner (exact f32, GNet::u), applies the

@@ -87,6 +87,29 @@ struct TrainGraph {
     uint64_t last_use = 0;
 };
 
+// One captured step of df_train_epoch (gather, gradient, update, cursor advance): slot 0 the
+// full batch, slot 1 the epoch's partial last batch.  Valid while the epoch's key
+// (df_train::ekey) and the buffers it names stand.
+struct EpochGraph {
+    int64_t count = 0, cap_gen = -1, partial_gen = -1;
+    int flow = -1;
+    int seen = 0;                     // eager runs of this step (captured on the second)
+    hipGraphExec_t exec = nullptr;
+};
+
+// What a captured epoch step names besides the trainer's own buffers.
+struct EpochKey {
+    const float* x_set = nullptr;
+    const float* theta_set = nullptr;
+    const int32_t* order = nullptr;
+    const double* step_lp = nullptr;
+    int64_t n_samples = 0, batchsize = 0;
+    bool operator==(const EpochKey& o) const {
+        return x_set == o.x_set && theta_set == o.theta_set && order == o.order && step_lp == o.step_lp &&
+               n_samples == o.n_samples && batchsize == o.batchsize;
+    }
+};
+
 // One device-side regather of a packed blob from the flat parameters (launch_repack, or
 // launch_repack_split for bf16x3 plane blobs).  The blob belongs to the chain or the trainer;
 // n = 0: the chain has no such blob, nothing launches.
@@ -179,6 +202,13 @@ struct df_train {
     int och_eta = -1;                // the rule df_train_adjust sets η of: the Adam, else the first Descent
     DevBuf d_sumsq, d_oblocks;       // float [tensors] Σ dx²; OptBlock [n_oblocks] of the update kernel
     int64_t n_oblocks = 0;
+    // df_train_epoch: the mini-batch staging buffers ((d, ecap) and (n, ecap), sized at the
+    // first use of a batchsize, only growing), the device cursor (int64 step index, then the
+    // int count of order_range_kernel) and the two captured steps, in slots of their own
+    DevBuf d_ex, d_eth, d_cursor;
+    int64_t ecap = 0;
+    EpochKey ekey;
+    EpochGraph eg[2];
 };
 
 namespace {
@@ -191,6 +221,10 @@ void free_all(df_train* t) {
     for (TrainGraph& g : t->graphs)
         if (g.exec) (void)hipGraphExecDestroy(g.exec);
     t->graphs.clear();
+    for (EpochGraph& g : t->eg) {
+        if (g.exec) (void)hipGraphExecDestroy(g.exec);
+        g = EpochGraph{};
+    }
     if (t->cap_stream) (void)hipStreamDestroy(t->cap_stream);
     t->cap_stream = nullptr;
 }
@@ -1617,6 +1651,168 @@ int df_train_step_graph(df_train* t, const float* x, const float* theta_raw, int
     g->last_use = now;
     e = hipGraphLaunch(g->exec, st);
     return e == hipSuccess ? DF_OK : hip_err(e, "hipGraphLaunch(train step)");
+}
+
+int df_batch_gather(float* x_out, float* theta_out, const float* x_set, const float* theta_set, int d, int n,
+                    int64_t n_samples, const int32_t* order, int64_t first, int64_t count, void* stream) {
+    if (d < 1 || n < 0) return set_err(DF_ERR_INVALID, "df_batch_gather: d >= 1 and n >= 0");
+    if (count < 0 || n_samples < 0) return set_err(DF_ERR_SHAPE, "negative sample count");
+    if (n_samples >= (int64_t)1 << 31) return set_err(DF_ERR_SHAPE, "a resident set holds fewer than 2^31 samples");
+    if (first < 0 || first + count > n_samples)
+        return set_err(DF_ERR_INVALID, "df_batch_gather: [first, first + count) must lie inside [0, n_samples)");
+    if (count == 0) return DF_OK;
+    if (!x_out || !x_set || (n > 0 && (!theta_out || !theta_set))) return set_err(DF_ERR_INVALID, "null array");
+    const hipError_t e = launch_batch_gather(x_out, theta_out, x_set, theta_set, d, n, n_samples, order, first,
+                                             nullptr, 0, count, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? DF_OK : hip_err(e, "batch gather launch");
+}
+
+}  // extern "C"
+
+namespace {
+
+// One step of an epoch on `st`: the mini-batch at the device cursor into the staging
+// buffers, df_train_step on it (Σ logpdf into the trainer's own double), then the cursor
+// moves on and leaves the step's Σ logpdf in step_lp.  Under df_train_set_debug a refused
+// update returns before the advance.
+int epoch_step(df_train* t, int64_t count, hipStream_t st) {
+    const Plan& P = t->c->plan;
+    const EpochKey& k = t->ekey;
+    int64_t* cursor = t->d_cursor.as<int64_t>();
+    float* ex = t->d_ex.as<float>();
+    float* eth = P.n > 0 ? t->d_eth.as<float>() : nullptr;
+    hipError_t e = launch_batch_gather(ex, eth, k.x_set, k.theta_set, P.d, P.n, k.n_samples, k.order, 0, cursor,
+                                       k.batchsize, count, st);
+    if (e != hipSuccess) return hip_err(e, "batch gather launch");
+    int rc = df_train_gradient(t, ex, eth, count, count, nullptr, st);
+    if (rc == DF_OK) rc = df_train_apply(t, st);
+    if (rc != DF_OK) return rc;
+    e = launch_cursor_advance(cursor, t->d_lpsum.as<const double>(), const_cast<double*>(k.step_lp), st);
+    return e == hipSuccess ? DF_OK : hip_err(e, "cursor advance launch");
+}
+
+void drop(EpochGraph& g) {
+    if (g.exec) (void)hipGraphExecDestroy(g.exec);
+    g = EpochGraph{};
+}
+
+// epoch_step as df_train_step_graph runs its step: eagerly at first sight (every buffer the
+// step needs is allocated then), captured on the trainer's private stream at the second,
+// replayed from then on; a capture that names reallocated buffers, an adjusted η or the
+// other θ convention is dropped first.
+int epoch_step_graph(df_train* t, EpochGraph& g, int64_t count, hipStream_t st) {
+    const int flow_now = theta_flow(t);
+    if (g.count != count || g.cap_gen != t->cap_gen || g.partial_gen != t->c->partial_gen || g.flow != flow_now)
+        drop(g);
+    if (g.exec) {
+        const hipError_t e = hipGraphLaunch(g.exec, st);
+        return e == hipSuccess ? DF_OK : hip_err(e, "hipGraphLaunch(epoch step)");
+    }
+    if (!g.seen) {
+        const int rc = epoch_step(t, count, st);
+        g.seen = 1;
+        g.count = count;
+        g.flow = flow_now;
+        g.cap_gen = t->cap_gen;
+        g.partial_gen = t->c->partial_gen;
+        return rc;
+    }
+    if (!t->cap_stream && hipStreamCreateWithFlags(&t->cap_stream, hipStreamNonBlocking) != hipSuccess)
+        return set_err(DF_ERR_HIP, "hipStreamCreate failed");
+    hipError_t e = hipStreamBeginCapture(t->cap_stream, hipStreamCaptureModeThreadLocal);
+    if (e != hipSuccess) return hip_err(e, "hipStreamBeginCapture");
+    const int rc = epoch_step(t, count, t->cap_stream);
+    hipGraph_t graph = nullptr;
+    e = hipStreamEndCapture(t->cap_stream, &graph);
+    if (rc != DF_OK || e != hipSuccess || !graph) {
+        if (graph) (void)hipGraphDestroy(graph);
+        return rc != DF_OK ? rc : hip_err(e, "hipStreamEndCapture");
+    }
+    if (g.cap_gen != t->cap_gen || g.partial_gen != t->c->partial_gen) {  // a buffer moved while capturing
+        (void)hipGraphDestroy(graph);
+        return set_err(DF_ERR_HIP, "internal: training buffers reallocated during graph capture");
+    }
+    e = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+    if (e != hipSuccess) {
+        g.exec = nullptr;
+        return hip_err(e, "hipGraphInstantiate(epoch step)");
+    }
+    e = hipGraphLaunch(g.exec, st);
+    return e == hipSuccess ? DF_OK : hip_err(e, "hipGraphLaunch(epoch step)");
+}
+
+}  // namespace
+
+extern "C" {
+
+int df_train_epoch(df_train* t, const float* x_set, const float* theta_set, int64_t n_samples, const int32_t* order,
+                   int64_t batchsize, double* step_logpdf_sum, int64_t* steps_done, void* stream) {
+    if (!t) return set_err(DF_ERR_INVALID, "null trainer");
+    if (steps_done) *steps_done = 0;
+    if (batchsize <= 0) return set_err(DF_ERR_INVALID, "batchsize must be >= 1");
+    if (n_samples < 0) return set_err(DF_ERR_SHAPE, "negative sample count");
+    if (n_samples == 0) return DF_OK;
+    if (n_samples >= (int64_t)1 << 31) return set_err(DF_ERR_SHAPE, "a resident set holds fewer than 2^31 samples");
+    if (!x_set) return set_err(DF_ERR_INVALID, "null input array");
+    df_chain* c = t->c;
+    const Plan& P = c->plan;
+    if (P.n > 0 && !theta_set)
+        return set_err(DF_ERR_SHAPE, "dimensions θ must match (n, dims...) with n number of trained parameters");
+    if (theta_flow(t) < 0)
+        return set_err(DF_ERR_INVALID, "θ bounds not set (df_chain_set_theta_bounds) for DF_THETA_RAW");
+    DeviceGuard gd(c->device);
+    if (!gd.ok) return set_err(DF_ERR_HIP, "hipSetDevice failed");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!t->d_cursor.get() && t->d_cursor.alloc(16) != hipSuccess)
+        return set_err(DF_ERR_NOMEM, "hipMalloc failed (epoch cursor)");
+    int64_t* cursor = t->d_cursor.as<int64_t>();
+
+    // the one synchronisation of the call: an order is checked before any step is enqueued
+    if (order) {
+        int* d_bad = reinterpret_cast<int*>(cursor + 1);
+        int bad = 0;
+        hipError_t e = launch_order_range(order, n_samples, d_bad, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return hip_err(e, "order check");
+        if (bad > 0) {
+            char msg[128];
+            std::snprintf(msg, sizeof msg, "df_train_epoch: %d of the %lld order entries lie outside [0, n_samples)",
+                          bad, (long long)n_samples);
+            return set_err(DF_ERR_INVALID, msg);
+        }
+    }
+
+    // staging for one mini-batch; the captured steps name it and everything in the key
+    const int64_t full = std::min(batchsize, n_samples);
+    const EpochKey key{x_set, theta_set, order, step_logpdf_sum, n_samples, batchsize};
+    if (full > t->ecap) {
+        for (EpochGraph& g : t->eg) drop(g);
+        t->ecap = 0;
+        if (t->d_ex.alloc(sizeof(float) * (size_t)full * P.d) != hipSuccess ||
+            (P.n > 0 && t->d_eth.alloc(sizeof(float) * (size_t)full * P.n) != hipSuccess))
+            return set_err(DF_ERR_NOMEM, "hipMalloc failed (mini-batch staging)");
+        t->ecap = full;
+    }
+    if (!(key == t->ekey))
+        for (EpochGraph& g : t->eg) drop(g);
+    t->ekey = key;
+
+    hipError_t e = hipMemsetAsync(cursor, 0, sizeof(int64_t), st);
+    if (e != hipSuccess) return hip_err(e, "hipMemsetAsync");
+    const int64_t steps = (n_samples + batchsize - 1) / batchsize;
+    for (int64_t i = 0; i < steps; ++i) {
+        const int64_t count = std::min(batchsize, n_samples - i * batchsize);
+        // debug mode: the per-step loss check synchronises, so the steps run eagerly
+        const int rc = t->debug ? epoch_step(t, count, st) : epoch_step_graph(t, t->eg[count == full ? 0 : 1], count, st);
+        if (rc != DF_OK) {
+            if (steps_done) *steps_done = i;
+            return rc;
+        }
+    }
+    if (steps_done) *steps_done = steps;
+    return DF_OK;
 }
 
 int df_train_set_debug(df_train* t, int on) {

@@ -257,6 +257,30 @@ class HIPTrainer:
                                                 C.c_int64(n_total), _ptr(lpsum), _stream(self.device)),
                    "df_train_step_graph")
 
+    def gather(self, x_out, theta_out, x_set, theta_set, n_samples: int, order, first: int, count: int):
+        """df_batch_gather on flat device buffers: samples ``order[first : first + count]`` of the
+        resident set (``x_set`` (n_samples·d,), ``theta_set`` (n_samples·n,), Julia order; ``order``
+        an int32 device tensor or None for ``first + j``) into the first ``count`` samples of
+        ``x_out`` / ``theta_out``."""
+        _lib.check(self.lib.df_batch_gather(_ptr(x_out), _ptr(theta_out), _ptr(x_set), _ptr(theta_set),
+                                            C.c_int(self.chain.d), C.c_int(self.chain.n), C.c_int64(n_samples),
+                                            _ptr(order), C.c_int64(first), C.c_int64(count), _stream(self.device)),
+                   "df_batch_gather")
+
+    def epoch(self, x_set, theta_set, n_samples: int, order, batchsize: int, step_lp=None) -> int:
+        """df_train_epoch: one epoch of mini-batch steps on a resident set, enqueued without
+        waiting for them.  ``order``: an int32 device tensor of ``n_samples`` indices, or None
+        for the set's own order; ``step_lp``: a float64 device tensor with one entry per step
+        (ceil(n_samples / batchsize)) for every step's Σ logpdf, or None.  Returns the number of
+        steps enqueued, also kept in ``steps_done``; when debug mode refuses a step
+        (NonFiniteError), ``steps_done`` is that step's index."""
+        done = C.c_int64(0)
+        rc = self.lib.df_train_epoch(self.handle, _ptr(x_set), _ptr(theta_set), C.c_int64(n_samples), _ptr(order),
+                                     C.c_int64(batchsize), _ptr(step_lp), C.byref(done), _stream(self.device))
+        self.steps_done = int(done.value)
+        _lib.check(rc, "df_train_epoch")
+        return self.steps_done
+
     def adjust(self, eta: float) -> None:
         """``Optimisers.adjust!(state, η)`` (df_train_adjust): a new η for the chain's Adam, or
         without one its first Descent.  The moments and βᵗ are kept; captured steps are
@@ -422,7 +446,8 @@ def _nonfinite(v: float) -> bool:
 
 
 def train_(flow, data, state: TrainState, epochs: int = 100, batchsize: int = 64, shuffle: bool = True,
-           verbose: bool = True, debug: bool = False, rng=None, group=None, graphs: bool = True, comm=None):
+           verbose: bool = True, debug: bool = False, rng=None, group=None, graphs: bool = True, comm=None,
+           loader: str = "host", return_step_losses: bool = False):
     """``train!(flow, data, opt_state; epochs, batchsize, shuffle, verbose, debug)`` — src/Flows.jl:380-445.
 
     Per epoch: mini-batches of the training split (Flux.DataLoader: reshuffled
@@ -447,7 +472,27 @@ def train_(flow, data, state: TrainState, epochs: int = 100, batchsize: int = 64
     persistent staging buffer and the step (reverse sweep, reduction, Adam,
     repack) is replayed as one hipGraph (``graphs``; df_train_step_graph),
     which removes the per-launch host overhead that dominates the reference's
-    default batchsize of 64."""
+    default batchsize of 64.
+
+    ``loader``: ``"host"`` (the default) builds every mini-batch from the host as described
+    above.  ``"device"`` (one device, no ``comm`` / process group) keeps the training and
+    validation sets on the device, uploads each epoch's permutation in one copy and runs the
+    epoch's steps with one ``df_train_epoch`` call; the two epoch losses are read back
+    together, once per epoch.  It draws from ``rng`` as the host loader does, so parameters,
+    ``flow.train_loss`` and ``flow.valid_loss`` are bitwise the host loader's.
+    ``return_step_losses`` (device loader only): the call returns ``(result, losses)``,
+    ``result`` being what it returns otherwise and ``losses`` a float64 numpy array with the
+    loss ``-Σ logpdf / B`` of every mini-batch at the parameters before its step."""
+    if loader not in ("host", "device"):
+        raise _lib.ArgumentError(f'loader must be "host" or "device", got {loader!r}')
+    if loader == "device":
+        if comm is not None or _dist() is not None:
+            raise _lib.UnsupportedError('loader="device" runs on one device: data-parallel epochs need the '
+                                        'gradient all-reduce between the two halves of every step')
+        return _train_device(flow, data, state, epochs, batchsize, shuffle, verbose, debug, rng, return_step_losses)
+    if return_step_losses:
+        raise _lib.UnsupportedError('return_step_losses needs loader="device" (the host loader would have to '
+                                    'synchronise at every step to read the loss)')
     import torch
 
     from .parallel import shard_range
@@ -536,6 +581,79 @@ def train_(flow, data, state: TrainState, epochs: int = 100, batchsize: int = 64
             print(f"epoch: {len(flow.train_loss)} | train_loss = {train_loss}, valid_loss = {valid_loss}")
     state.sync_model()
     return (None, None) if debug else None
+
+
+def _train_device(flow, data, state: TrainState, epochs, batchsize, shuffle, verbose, debug, rng, return_step_losses):
+    """``train_(..., loader="device")``: both sets resident on the device, one ``df_train_epoch``
+    call and one read-back per epoch."""
+    import torch
+
+    if int(batchsize) <= 0:
+        raise _lib.ArgumentError("batchsize must be >= 1")
+    rng = rng if rng is not None else np.random.default_rng()
+    tr = state.trainer
+    tr.set_debug(debug)
+    dev = tr.device
+    n = flow.n
+    h = flow.hip()
+    x_tr, th_tr = data.training_data()
+    x_va, th_va = data.validation_data()
+    xt = as_julia_device(x_tr, flow.d, dev, "x")[0]             # (N*d,) Julia order, uploaded once
+    tt = as_julia_device(th_tr, n, dev, "θ")[0] if n > 0 else None
+    xv = as_julia_device(x_va, flow.d, dev, "x")[0]
+    tv = as_julia_device(th_va, n, dev, "θ")[0] if n > 0 else None
+    N, Nv = x_tr.shape[1], x_va.shape[1]
+    steps = -(-N // int(batchsize))
+    order_dev = torch.empty(N, dtype=torch.int32, device=dev) if shuffle else None
+    # [Σ logpdf of every step | Σ over the training set | Σ over the validation set]: one copy per epoch
+    sums = torch.zeros(steps + 2, dtype=torch.float64, device=dev)
+    step_losses = []
+    ret = lambda r: (r, np.concatenate(step_losses) if step_losses else np.zeros(0)) if return_step_losses else r
+    for _ in range(epochs):
+        order = rng.permutation(N) if shuffle else None
+        if shuffle:
+            order_dev.copy_(torch.from_numpy(order.astype(np.int32)))
+        try:
+            tr.epoch(xt, tt, N, order_dev, batchsize, sums[:steps] if steps else None)
+        except _lib.NonFiniteError as e:
+            # as the host loader: the model at the last good parameters, the refused batch's
+            # diagnostics (rebuilt on the host from the order and the step's index), ArgumentError
+            state.sync_model()
+            b0 = tr.steps_done * int(batchsize)
+            idx = order[b0:b0 + batchsize] if shuffle else np.arange(b0, min(b0 + batchsize, N))
+            ii = torch.as_tensor(idx, device=dev)
+            xb = xt.view(N, flow.d).index_select(0, ii)
+            tb = tt.view(N, n).index_select(0, ii) if tt is not None else None
+            xv_, tv_ = xb.T, (tb.T if tb is not None else None)
+            z, ldj = flow.backward(xv_, tv_)
+            s = flow.hip().logpdf_sum(xv_, tv_)[0]
+            print(f"{-float(s.item()) / max(idx.shape[0], 1)}, {ldj.cpu().numpy()}, {z.cpu().numpy()}")
+            raise _lib.ArgumentError(str(e)) from e
+        sums[steps:].zero_()
+        if N > 0:
+            h.run_logpdf_sum(xt, tt, sums[steps:steps + 1], N)
+        if Nv > 0:
+            h.run_logpdf_sum(xv, tv, sums[steps + 1:], Nv)
+        got = sums.cpu().numpy()
+        if return_step_losses:
+            sizes = np.minimum(int(batchsize), N - np.arange(steps) * int(batchsize))
+            step_losses.append(-got[:steps] / sizes)
+        train_loss = -float(got[steps]) / float(N) if N > 0 else float("nan")
+        valid_loss = -float(got[steps + 1]) / float(Nv) if Nv > 0 else float("nan")
+        flow.train_loss.append(train_loss)
+        if debug and _nonfinite(train_loss):
+            print(f"Problem with train loss {train_loss}")
+            state.sync_model()
+            return ret(_backward_set(flow, x_tr, th_tr))
+        flow.valid_loss.append(valid_loss)
+        if debug and _nonfinite(valid_loss):
+            print(f"Problem with valid loss {valid_loss}")
+            state.sync_model()
+            return ret(_backward_set(flow, x_va, th_va))
+        if verbose:
+            print(f"epoch: {len(flow.train_loss)} | train_loss = {train_loss}, valid_loss = {valid_loss}")
+    state.sync_model()
+    return ret((None, None) if debug else None)
 
 
 def _backward_set(flow, x, th):

@@ -388,6 +388,50 @@ int df_train_step(df_train* t, const float* x, const float* theta_raw, int64_t b
  * data parallelism (the gradient all-reduce sits between the two halves). */
 int df_train_step_graph(df_train* t, const float* x, const float* theta_raw, int64_t batch, int64_t n_total,
                         double* logpdf_sum, void* stream);
+/* ---- device-resident epochs (additive to ABI 5) -------------------------------
+ * A data set that stays on the device: x_set (d, n_samples) and theta_set (n, n_samples),
+ * column-major like every batch (each sample's values contiguous), and an optional order
+ * of n_samples int32 sample indices (a permutation for a shuffled epoch; repeats allowed).
+ *
+ * df_batch_gather: one mini-batch out of the set, for hosts that keep their own loop.
+ *   x_out[:, j] = x_set[:, order[first + j]],  theta_out[:, j] = theta_set[:, order[first + j]]
+ * for j < count (order == NULL: sample first + j).  One launch serves both arrays;
+ * n == 0: x alone, the θ pointers are ignored.  Stream-ordered, no synchronisation; nothing
+ * past `count` samples of the outputs is written; count == 0 writes nothing.
+ * [first, first + count) outside [0, n_samples): DF_ERR_INVALID.  The order's entries are
+ * NOT checked here (that costs a synchronisation, see df_train_epoch): an entry outside
+ * [0, n_samples) gathers sample 0 instead, it never becomes an address. */
+int df_batch_gather(float* x_out, float* theta_out, const float* x_set, const float* theta_set, int d, int n,
+                    int64_t n_samples, const int32_t* order, int64_t first, int64_t count, void* stream);
+/* One epoch of train!'s mini-batch loop (src/Flows.jl:396-417) on a resident set:
+ * ceil(n_samples / batchsize) steps, step i being df_train_step on the samples
+ * order[i·batchsize ... min((i+1)·batchsize, n_samples)) (the partial last batch is kept,
+ * as Flux.DataLoader keeps it), with the trainer's optimiser (df_train_create_opt,
+ * df_train_adjust) and θ convention (df_train_set_theta_input).  Parameters and optimiser
+ * state afterwards are bitwise those of that loop of df_train_step calls.
+ * step_logpdf_sum (device, one double per step, may be NULL) receives every step's
+ * Σ logpdf at the parameters before its update (the step's loss is -Σ/batch).
+ * The mini-batches are gathered on the device into staging buffers the trainer owns
+ * (sized at the first use of a batchsize); the position in the epoch is a device counter,
+ * so every full-batch step is the same captured graph (a second one serves the partial
+ * last batch): gather, gradient, update and counter advance replay as one launch per
+ * step.  The two graphs live in slots of their own beside df_train_step_graph's, are
+ * captured the second time their step is seen with the same (x_set, theta_set,
+ * n_samples, order, batchsize, step_logpdf_sum), and are re-captured after
+ * df_train_adjust or when a buffer they name was reallocated.
+ * The call is stream-ordered and returns without waiting for the steps.  With an order it
+ * synchronises the stream once, before the first step, to check the order: entries outside
+ * [0, n_samples) return DF_ERR_INVALID (the message names their number) and no step is
+ * enqueued.  With order == NULL it does not synchronise.  No step costs a host
+ * synchronisation or a host-to-device copy.
+ * Under df_train_set_debug the steps run eagerly with the per-step loss check: a
+ * non-finite loss returns DF_ERR_NONFINITE, leaves the parameters at the last good step and
+ * writes the refused step's index to *steps_done.  Otherwise *steps_done (host, may be
+ * NULL) is the number of steps enqueued.
+ * n_samples == 0: DF_OK, nothing runs.  batchsize <= 0 or x_set == NULL: DF_ERR_INVALID.
+ * n_samples >= 2^31: DF_ERR_SHAPE.  Not for data parallelism (df_train_step_dist). */
+int df_train_epoch(df_train* t, const float* x_set, const float* theta_set, int64_t n_samples, const int32_t* order,
+                   int64_t batchsize, double* step_logpdf_sum, int64_t* steps_done, void* stream);
 /* train!(...; debug=true) (src/Flows.jl:404-409): when on, df_train_apply
  * (and the steps built on it) first reads the Σ logpdf of the last gradient
  * evaluation back to the host; if the loss is NaN or ±Inf the parameters are
