@@ -13,8 +13,8 @@ from .axes import CouplingAxes, is_reverse, reverse
 from .chains import FlowChain, backward, concatenate, forward, forward_, forward_inplace
 from .data import (DataArrays, DataPartition, MetaData, dflt_theta, maximum_theta, minimum_theta,
                    normalize_input, resize_output)
-from .flows import (Flow, MvNormal, logpdf, logpdf_grad, logpdf_grid, nll_partial_sum, pdf, predict, sample,
-                    training_loss, validation_loss)
+from .flows import (Box, Flow, HalfSpaces, MvNormal, Region, logpdf, logpdf_grad, logpdf_grid, nll_partial_sum, pdf,
+                    predict, sample, sample_with_rejection, training_loss, validation_loss)
 from .layers import (Chain, CouplingBlock, CouplingLayer, Dense, FlowElement, NICECouplingLayer,
                      NormalizationLayer, RNVPCouplingLayer, default_net)
 from .train import (Adam, AdamW, ClipGrad, ClipNorm, Descent, OptimiserChain, TrainState, WeightDecay, adjust_,

@@ -121,6 +121,15 @@ class df_opt_rule(C.Structure):
     _fields_ = [("kind", C.c_int32), ("p", C.c_float * 4)]
 
 
+# df_region (df_flow_sample_region)
+DF_REGION_MAX_HALFSPACES = 8
+
+
+class df_region(C.Structure):
+    _fields_ = [("d", C.c_int32), ("n_half", C.c_int32), ("lo", C.POINTER(C.c_float)),
+                ("hi", C.POINTER(C.c_float)), ("a", C.POINTER(C.c_float)), ("b", C.POINTER(C.c_float))]
+
+
 _FP = C.POINTER(C.c_float)
 _VP = C.c_void_p
 _I64 = C.c_int64
@@ -179,6 +188,8 @@ SIGNATURES = {
     "df_train_step_dist": (C.c_int, [_VP, _VP, _VP, _VP, _I64, _I64, _VP, _VP]),
     "df_flow_sample": (C.c_int, [_VP, _VP, _VP, C.c_int, _I64, C.c_uint64, C.c_uint64, _VP]),
     "df_random_normal": (C.c_int, [_VP, _I64, C.c_uint64, C.c_uint64, _VP]),
+    "df_flow_sample_region": (C.c_int, [_VP, _VP, _VP, _I64, C.POINTER(df_region), _I64, _I64, C.c_uint64,
+                                        C.c_uint64, C.POINTER(_I64), C.POINTER(_I64), _VP]),
     "df_flow_logpdf_grid": (C.c_int, [_VP, _VP, C.POINTER(_I64), _I64, _I64, _VP, _I64, _VP]),
     "df_theta_broadcast": (C.c_int, [_VP, _VP, C.c_int, _I64, _VP]),
     "df_chain_clock_probe": (C.c_int, [_VP, C.c_int]),

@@ -121,6 +121,16 @@ struct df_chain {
     // staging of df_flow_logpdf_grid: one chunk's [x (d, chunk) | θ (n, chunk)]; only grows
     DevBuf d_grid_ws;
     int64_t grid_ws_cap = 0;  // floats
+    // workspaces of df_flow_sample_region (df_reject.hip), sized for one round of rej_cap
+    // candidates; they only grow
+    DevBuf d_rej_cand;    // float [d · rej_cap]: the round's candidates
+    DevBuf d_rej_theta;   // float [n · rej_cap]: the θ broadcast
+    DevBuf d_rej_mask;    // uint64 [rej_cap / 64]: one acceptance ballot per wave
+    DevBuf d_rej_base;    // uint32 [rej_cap / 64]: accepted before each wave, within the round
+    DevBuf d_rej_region;  // float [lo (d) | hi (d) | a (n_half · d) | b (n_half)]
+    DevBuf d_rej_cnt;     // int64 [accepted | tried | round base | -]
+    int64_t rej_cap = 0;  // candidates
+    std::vector<float> h_rej_region;  // the host block d_rej_region was last uploaded from
     ~df_chain() {
         if (d_theta_ws) (void)hipFree(d_theta_ws);
     }

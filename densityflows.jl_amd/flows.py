@@ -13,8 +13,8 @@ from .chains import FlowChain, _n_of
 from .data import DataArrays, MetaData, maximum_theta, minimum_theta
 from .hip import as_julia_device, julia_empty
 
-__all__ = ["Flow", "MvNormal", "predict", "sample", "logpdf", "logpdf_grid", "logpdf_grad", "pdf",
-           "training_loss", "validation_loss", "nll_partial_sum"]
+__all__ = ["Flow", "MvNormal", "predict", "sample", "sample_with_rejection", "Box", "HalfSpaces", "Region",
+           "logpdf", "logpdf_grid", "logpdf_grad", "pdf", "training_loss", "validation_loss", "nll_partial_sum"]
 
 LOG2PI = float(np.log(2.0 * np.pi))
 
@@ -160,6 +160,198 @@ def sample(flow: Flow, dims: Union[int, Tuple[int, ...]], theta=None, rng=None, 
             thb, _, _ = as_julia_device(theta, flow.n, dev, "θ")
     h.run_sample(buf, thb, bcast, batch, seed, offset)
     return r
+
+
+# ---------------------------------------------------------------------------
+# truncated sampling — src/Flows.jl:196-229
+# ---------------------------------------------------------------------------
+
+def _f32_no_nan(a, what):
+    a = np.asarray(a, dtype=np.float32)
+    if np.isnan(a).any():
+        raise _lib.ArgumentError(f"NaN in {what}")
+    return a
+
+
+class Box:
+    """``lo[k] <= x[k] <= hi[k]`` in every dimension; ±inf allowed; a scalar bound holds for
+    every dimension.  ``lo > hi`` is legal: the box is empty."""
+
+    def __init__(self, lo=-np.inf, hi=np.inf):
+        self.lo, self.hi = _f32_no_nan(lo, "the box's lo"), _f32_no_nan(hi, "the box's hi")
+        for v, name in ((self.lo, "lo"), (self.hi, "hi")):
+            if v.ndim > 1:
+                raise _lib.DimensionMismatch(f"the box's {name} must be a scalar or a vector of d values")
+        if self.lo.ndim == 1 and self.hi.ndim == 1 and self.lo.shape != self.hi.shape:
+            raise _lib.DimensionMismatch("the box's lo and hi differ in length")
+
+    def arrays(self, d: int):
+        out = []
+        for v, name in ((self.lo, "lo"), (self.hi, "hi")):
+            if v.ndim == 1 and v.shape[0] != d:
+                raise _lib.DimensionMismatch(f"the box's {name} has {v.shape[0]} values, the flow has d = {d}")
+            out.append(np.ascontiguousarray(np.broadcast_to(v, (d,)), dtype=np.float32))
+        return tuple(out)
+
+
+class HalfSpaces:
+    """``Σ_k A[h, k]·x[k] <= b[h]`` for each of up to 8 rows of ``A`` (h, d); one constraint
+    may be given as a vector and a scalar.  The sum is taken left to right in Float32."""
+
+    def __init__(self, A, b):
+        A, b = _f32_no_nan(A, "the half-spaces' A"), _f32_no_nan(b, "the half-spaces' b")
+        if A.ndim == 1 and b.ndim == 0:
+            A, b = A[None, :], b[None]
+        if A.ndim != 2 or b.ndim != 1 or A.shape[0] != b.shape[0]:
+            raise _lib.DimensionMismatch("half-spaces need A of size (h, d) and b of h values")
+        if A.shape[0] > _lib.DF_REGION_MAX_HALFSPACES:
+            raise _lib.UnsupportedError(f"a region holds at most {_lib.DF_REGION_MAX_HALFSPACES} half-spaces")
+        if A.shape[0] > 0 and A.shape[1] < 1:
+            raise _lib.DimensionMismatch("half-spaces need A of size (h, d) with d >= 1")
+        self.A, self.b = np.ascontiguousarray(A), np.ascontiguousarray(b)
+
+    def arrays(self, d: int):
+        if self.A.shape[0] > 0 and self.A.shape[1] != d:
+            raise _lib.DimensionMismatch(f"the half-spaces' A has {self.A.shape[1]} columns, the flow has d = {d}")
+        return self.A.reshape(-1, d), self.b
+
+
+class Region:
+    """A :class:`Box` and / or :class:`HalfSpaces`: the ``condition`` of
+    :func:`sample_with_rejection` that is evaluated on the device."""
+
+    def __init__(self, box: Optional[Box] = None, halfspaces: Optional[HalfSpaces] = None):
+        if box is not None and not isinstance(box, Box):
+            raise _lib.ArgumentError("Region: box must be a Box")
+        if halfspaces is not None and not isinstance(halfspaces, HalfSpaces):
+            raise _lib.ArgumentError("Region: halfspaces must be a HalfSpaces")
+        self.box, self.halfspaces = box, halfspaces
+
+    def arrays(self, d: int):
+        """(lo (d), hi (d), A (h, d), b (h)) in Float32, as the library takes them."""
+        lo, hi = (self.box if self.box is not None else Box()).arrays(d)
+        if self.halfspaces is not None:
+            A, b = self.halfspaces.arrays(d)
+        else:
+            A, b = np.zeros((0, d), np.float32), np.zeros(0, np.float32)
+        return lo, hi, A, b
+
+
+# df_reject.hip's adaptive schedule (round = 0), restated: the closure path cuts the
+# candidate stream where the library does
+_REJ_MIN_ROUND, _REJ_MAX_ROUND = 1 << 10, 1 << 22
+
+
+def _round_up4(v: int) -> int:
+    return (v + 3) // 4 * 4
+
+
+def _first_round(n_want: int) -> int:
+    return _round_up4(min(max(2 * min(n_want, _REJ_MAX_ROUND), _REJ_MIN_ROUND), _REJ_MAX_ROUND))
+
+
+def _next_round(remaining: int, examined: int, accepted: int, prev: int) -> int:
+    want = 2 * prev if accepted == 0 else -(-(remaining * examined * 5) // (accepted * 4)) + 64
+    return _round_up4(min(max(want, _REJ_MIN_ROUND), _REJ_MAX_ROUND))
+
+
+def _reject_closure(h, condition, theta, thb, buf, n_want, max_tries, round, seed, offset):
+    """The host form: the library's candidate stream through ``run_sample`` round by round,
+    ``condition(x, θ)`` per candidate in order, the first ``n_want`` kept → (tried, accepted)."""
+    import torch
+
+    d = h.d
+    R = _round_up4(round) if round > 0 else _first_round(n_want)
+    k0 = accepted = 0
+    out = buf.view(-1, d)
+    while k0 < max_tries:
+        cand = torch.empty(R * d, dtype=torch.float32, device=h.device)
+        h.run_sample(cand, thb, thb is not None, R, seed, offset + d * (k0 // 4))
+        rows = cand.cpu().numpy().reshape(R, d)
+        count = min(R, max_tries - k0)
+        keep = []
+        for i in range(count):
+            if condition(rows[i], theta):
+                keep.append(i)
+                if accepted + len(keep) == n_want:
+                    break
+        if keep:
+            out[accepted:accepted + len(keep)].copy_(torch.from_numpy(rows[keep]).to(h.device))
+        accepted += len(keep)
+        if accepted == n_want:
+            return k0 + keep[-1] + 1, accepted
+        k0 += count
+        if round == 0:
+            R = _next_round(n_want - accepted, k0, accepted, R)
+    return k0, accepted
+
+
+def sample_with_rejection(condition, flow: Flow, dims: Union[int, Tuple[int, ...]], theta: tuple = (), m: int = 100,
+                          rng=None, seed: Optional[int] = None, offset: int = 0, round: int = 0,
+                          return_counts: bool = False):
+    """``sample_with_rejection([rng, ] condition, flow, dims, θ [, m])`` — src/Flows.jl:196-229:
+    the first prod(dims) samples of the flow at the NTuple θ that satisfy ``condition``,
+    shape (d, dims...) in Julia memory order.  Candidate k is column k of
+    ``sample(flow, N, θ, seed=seed, offset=offset)``; at most ``m``·prod(dims) candidates are
+    examined, and if they do not fill the result an ArgumentError is raised, as the
+    reference throws (its ``.tried`` / ``.accepted`` hold the counts).
+
+    ``condition`` is a :class:`Region` (or a :class:`Box` / :class:`HalfSpaces`): one library
+    call (``df_flow_sample_region``), predicate and order-preserving compaction on the
+    device, one small read-back per round of candidates.  Or the reference's closure
+    ``condition(x, θ) -> Bool`` with ``x`` a length-d Float32 vector: a host loop over the
+    same candidate stream, for predicates a region cannot state; for a closure that states
+    a region's predicate both forms return the same arrays.  ``round``: candidates per round
+    (0: chosen from ``dims`` and the acceptance rate so far); the result does not depend on
+    it.  ``return_counts``: (x, tried, accepted), tried = 1 + the index of the candidate that
+    filled the last slot — accepted / tried estimates the region's probability."""
+    import torch
+
+    if isinstance(dims, (int, np.integer)):
+        dims = (dims,)
+    dims = tuple(int(v) for v in dims)
+    if any(v < 0 for v in dims):
+        raise _lib.DimensionMismatch("dims must be non-negative")
+    if not isinstance(theta, tuple):
+        raise _lib.ArgumentError("sample_with_rejection takes θ as an NTuple of n values (one condition for "
+                                 "every sample); the reference has no method for an array θ")
+    if len(theta) != flow.n:
+        raise _lib.DimensionMismatch("dimensions θ must match (n, dims...) with n number of trained parameters")
+    if isinstance(condition, (Box, HalfSpaces)):
+        condition = Region(condition, None) if isinstance(condition, Box) else Region(None, condition)
+    if isinstance(condition, Region):
+        region = condition.arrays(flow.d)
+    elif callable(condition):
+        region = None
+    else:
+        raise _lib.ArgumentError("condition must be a Region, a Box, HalfSpaces or a callable condition(x, θ)")
+    m, round, offset = int(m), int(round), int(offset)
+    if m < 0 or round < 0:
+        raise _lib.DimensionMismatch("m and round must be non-negative")
+    if seed is None:
+        rng = rng if rng is not None else np.random.default_rng()
+        seed = int(rng.integers(0, 2**63 - 1, dtype=np.int64)) * 2 + int(rng.integers(0, 2))
+    n_want = int(np.prod(dims)) if dims else 1
+    max_tries = m * n_want
+    h = flow.hip()
+    buf, r = julia_empty(flow.d, dims, h.device)
+    thb = None
+    if flow.n > 0:
+        thb = torch.tensor([float(np.float32(v)) for v in theta], dtype=torch.float32, device=h.device)
+    tried = accepted = 0
+    if n_want > 0:
+        with torch.cuda.device(h.device):
+            if region is not None:
+                tried, accepted = h.run_sample_region(buf, thb, n_want, *region, max_tries, round, seed, offset)
+            else:
+                tried, accepted = _reject_closure(h, condition, theta, thb, buf, n_want, max_tries, round, seed,
+                                                  offset)
+                if accepted < n_want:
+                    e = _lib.ArgumentError("sample_with_rejection: Impossible to reach convergence of rejection "
+                                           f"sampling: {accepted} of {n_want} accepted after {tried} candidates")
+                    e.tried, e.accepted = tried, accepted
+                    raise e
+    return (r, tried, accepted) if return_counts else r
 
 
 def logpdf(flow: Flow, x, theta=None):

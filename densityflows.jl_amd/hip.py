@@ -288,6 +288,33 @@ class HIPChain:
                                            C.c_int64(batch), C.c_uint64(seed), C.c_uint64(offset),
                                            _stream(self.device)), "sample")
 
+    def run_sample_region(self, xbuf, thvec, n_want: int, lo, hi, A, b, max_tries: int, round: int, seed: int,
+                          offset: int = 0):
+        """df_flow_sample_region: the first ``n_want`` samples of the (seed, offset) candidate
+        stream inside the region into ``xbuf`` → (tried, accepted).  ``lo`` / ``hi``: d host
+        floats, ``A`` (n_half, d) and ``b`` (n_half); ``thvec``: ONE n-vector on the device.
+        When the slots are not filled within ``max_tries`` the ArgumentError raised carries
+        the counts as ``.tried`` and ``.accepted``."""
+        lo = np.ascontiguousarray(lo, dtype=np.float32).reshape(-1)
+        hi = np.ascontiguousarray(hi, dtype=np.float32).reshape(-1)
+        A = np.ascontiguousarray(A, dtype=np.float32).reshape(-1, max(lo.shape[0], 1))
+        b = np.ascontiguousarray(b, dtype=np.float32).reshape(-1)
+        if hi.shape != lo.shape or A.shape[0] != b.shape[0] or (A.shape[0] and A.shape[1] != lo.shape[0]):
+            raise _lib.DimensionMismatch("a region needs lo and hi of d values, A of size (n_half, d) and b of n_half")
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+        reg = _lib.df_region(lo.shape[0], A.shape[0], fp(lo), fp(hi), fp(A), fp(b))
+        tried, accepted = C.c_int64(0), C.c_int64(0)
+        rc = self.lib.df_flow_sample_region(self.handle, _ptr(xbuf), _ptr(thvec), C.c_int64(n_want), C.byref(reg),
+                                            C.c_int64(max_tries), C.c_int64(round), C.c_uint64(seed),
+                                            C.c_uint64(offset), C.byref(tried), C.byref(accepted),
+                                            _stream(self.device))
+        try:
+            _lib.check(rc, "sample_with_rejection")
+        except _lib.ArgumentError as e:
+            e.tried, e.accepted = tried.value, accepted.value
+            raise
+        return tried.value, accepted.value
+
     def random_normal(self, buf, count: int, seed: int, offset: int = 0):
         """df_random_normal: the draw df_flow_sample uses for the same (seed, offset)."""
         _lib.check(self.lib.df_random_normal(_ptr(buf), C.c_int64(count), C.c_uint64(seed), C.c_uint64(offset),

@@ -248,6 +248,58 @@ int df_flow_logpdf_grid(df_chain* chain, const float* axes, const int64_t* lens,
  * logpdf(flow, x, θ::Tuple) (src/Flows.jl:284, collect(θ) broadcast over the points). */
 int df_theta_broadcast(float* out, const float* theta, int n, int64_t batch, void* stream);
 
+/* ---- truncated sampling (additive to ABI 5) -----------------------------------
+ * sample_with_rejection(condition, flow, dims, θ, m) (src/Flows.jl:196-229) for a
+ * condition given as a region: the first n_want samples of the flow that lie inside it.
+ * The region (all HOST memory, Float32; NaN anywhere is DF_ERR_INVALID):
+ *   box          lo[k] <= x[k] <= hi[k] for each of the d dimensions; ±inf allowed; a NULL
+ *                lo / hi is -inf / +inf everywhere; lo > hi is legal and rejects everything
+ *   half-spaces  n_half in 0..DF_REGION_MAX_HALFSPACES rows of a (n_half, d), row by row:
+ *                acc = a[h][0]*x[0]; acc = acc + a[h][k]*x[k] for k = 1 .. d-1; acc <= b[h]
+ * Every operation is one Float32 operation, never contracted; comparisons are as written,
+ * so a NaN coordinate or a NaN sum rejects.  x is the flow's output (df_flow_sample's).
+ * theta_raw: DEVICE, ONE n-vector used for every candidate (the NTuple θ of the
+ * reference's signature); NULL for n = 0.
+ * Candidates: candidate k = 0, 1, ... is forward! of elements [d*k, d*k + d) of the
+ * df_random_normal(seed, offset) stream, so candidates 0..N-1 are what df_flow_sample
+ * (batch = N, seed, offset) returns — as far as df_flow_forward_inplace itself gives a
+ * sample the same bits at every batch size.  x_out (DEVICE, d * n_want floats) receives
+ * the first n_want accepted candidates in increasing k; that does not depend on the rounds.
+ *   accepted = min(n_want, accepted among the candidates examined)
+ *   tried    = 1 + the index of the candidate that filled the last slot; when the slots
+ *              were not filled, the number of candidates examined
+ * Candidates with index >= max_tries are never examined (the reference: max_tries = m *
+ * n_want, m = 100).  Slots not filled within max_tries: DF_ERR_INVALID, "Impossible to
+ * reach convergence of rejection sampling" and the counts; tried_out / accepted_out (HOST,
+ * either may be NULL) are still written, the first `accepted` rows of x_out are valid and
+ * the rest of x_out is untouched.
+ * Rounds: candidates are drawn, sent through forward! and examined a round at a time;
+ * a round is a multiple of 4 candidates (a Philox counter boundary; a requested size is
+ * rounded up) and is always drawn and forwarded whole, also past max_tries.  round > 0:
+ * that size for every round (at most 2^24, else DF_ERR_UNSUPPORTED).  round = 0: the first
+ * round holds 2 * n_want candidates, a later one remaining * examined / accepted with a
+ * quarter of head-room, each within [2^10, 2^22].
+ * SYNCHRONISATION: each round ends with a 16-byte device-to-host copy of the counters
+ * and a hipStreamSynchronize of `stream`; there is no other.  The call therefore returns
+ * with its work done, and is DF_ERR_INVALID inside a stream capture.  Its workspaces (one
+ * round's candidates, θ broadcast, ballots and bases; the region block; the counters)
+ * belong to the chain and only grow.
+ * Checked before any device work: NULL region, NULL chain -> DF_ERR_INVALID; region->d
+ * not the chain's d -> DF_ERR_SHAPE; n_half outside 0..8 -> DF_ERR_UNSUPPORTED; n_want,
+ * max_tries or round < 0 -> DF_ERR_SHAPE; n_want == 0 -> DF_OK, nothing runs; θ missing or
+ * bounds not set: df_flow_sample's errors. */
+#define DF_REGION_MAX_HALFSPACES 8
+typedef struct df_region {
+    int32_t d, n_half;
+    const float* lo;  /* d, or NULL */
+    const float* hi;  /* d, or NULL */
+    const float* a;   /* n_half * d */
+    const float* b;   /* n_half */
+} df_region;
+int df_flow_sample_region(df_chain* chain, float* x_out, const float* theta_raw, int64_t n_want,
+                          const df_region* region, int64_t max_tries, int64_t round, uint64_t seed, uint64_t offset,
+                          int64_t* tried_out, int64_t* accepted_out, void* stream);
+
 /* ---- training ---------------------------------------------------------------
  * train!(flow, data, opt_state; ...) src/Flows.jl:380-445: per batch
  *   grads = Flux.gradient(m -> loss(backward(m, x, θ)...), flow.model)   (:398-411)
