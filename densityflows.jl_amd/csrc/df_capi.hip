@@ -193,6 +193,8 @@ int df_chain_create(df_chain** out, const df_chain_desc* desc, int device) {
     c->no_wide = std::getenv("DF_NO_WIDE") && std::getenv("DF_NO_WIDE")[0] == '1';
     c->debug_launch = std::getenv("DF_DEBUG_LAUNCH") && std::getenv("DF_DEBUG_LAUNCH")[0] == '1';
     if (const char* e = std::getenv("DF_TILES")) c->force_tiles = std::atoi(e);
+    int grid_cus_env = 0;  // unset, 0 or invalid: n_cu (clamped once n_cu is known, below)
+    if (const char* e = std::getenv("DF_GRID_CUS")) grid_cus_env = std::atoi(e);
     if (const char* e = std::getenv("DF_SMALL_MAX")) c->small_max = std::max<int64_t>(0, std::atoll(e));
     if (const char* e = std::getenv("DF_SMALL_WAVES")) c->small_waves = std::atoi(e) == 1 ? 1 : 2;
     int rc = df::build_plan(desc, &c->plan, &err, c->exact ? 1 : 0);
@@ -302,6 +304,8 @@ int df_chain_create(df_chain** out, const df_chain_desc* desc, int device) {
     // occupancy by mode and tiles per wave (for the per-launch tile choice)
     if (hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || c->n_cu < 1)
         c->n_cu = 256;
+    // test aid (DF_GRID_CUS): the CU count the training and score grids are sized from
+    c->grid_cus = (grid_cus_env >= 1) ? std::min(grid_cus_env, c->n_cu) : c->n_cu;
     for (int mode = 0; mode < 4; ++mode)
         for (int t = 1; t <= P.tiles; ++t) {
             int blocks = 1;

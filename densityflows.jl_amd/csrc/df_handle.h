@@ -55,7 +55,8 @@ struct df_chain {
     int device = 0;
     bool exact = false;         // DF_F32_EXACT=1 at df_chain_create: exact-f32 kernels only (read once)
     // launch knobs, read from the environment once at df_chain_create (a launch does no
-    // getenv): DF_NO_WIDE=1, DF_DEBUG_LAUNCH=1, DF_TILES, DF_SMALL_MAX (-1: unset)
+    // getenv): DF_NO_WIDE=1, DF_DEBUG_LAUNCH=1, DF_TILES, DF_SMALL_MAX (-1: unset), DF_GRID_CUS
+    // (grid_cus below)
     bool no_wide = false;
     bool debug_launch = false;
     int force_tiles = 0;
@@ -83,6 +84,12 @@ struct df_chain {
     DevBuf d_sched;    // [fwd schedule | bwd schedule]
     DevBuf d_ulayers;  // specialised-kernel descriptors
     int n_cu = 0;
+    // DF_GRID_CUS (read once at df_chain_create; unset, 0 or invalid: n_cu; clamped to
+    // [1, n_cu]): the CU count the persistent training and score grids are sized from
+    // (df_train::grid, lgrid, score_grid and the Dense grid of the layer-wise sweep).  A test
+    // aid: a small value brings several trips of every batch loop down to small batches.  The
+    // chain-pass kernels (use_small, choose_tiles) keep n_cu.
+    int grid_cus = 0;
     int occ[4][df::kMaxTilesPerWave + 1] = {};  // resident workgroups per CU, by mode and tiles
     int tab_bytes = 0;
     size_t lds = 0;

@@ -960,8 +960,8 @@ int lsweep(df_train* t, const float* x, const float* theta, int64_t batch, float
     df_chain* c = t->c;
     const int64_t ntiles = (batch + 15) / 16;
     const unsigned dgrid =
-        (unsigned)std::max<int64_t>(1, std::min<int64_t>(c->n_cu, (ntiles + kWavesPerBlock * kLTiles - 1) /
-                                                                          (kWavesPerBlock * kLTiles)));
+        (unsigned)std::max<int64_t>(1, std::min<int64_t>(c->grid_cus, (ntiles + kWavesPerBlock * kLTiles - 1) /
+                                                                              (kWavesPerBlock * kLTiles)));
     LSweep s{};
     s.t = t;
     s.c = c;
@@ -1192,7 +1192,7 @@ int df_train_create_opt(df_train** out, df_chain* c, const df_opt_rule* rules, i
             b >= 1)
             occ = (i == 0) ? b : std::min(occ, b);
     }
-    t->grid = std::max(1, c->n_cu * occ);
+    t->grid = std::max(1, c->grid_cus * occ);
     if (t->layerwise) {
         // (the limits LSweep::launch holds every request against; derivation at the constants)
         e = set_ldense_lds_limit(kLdenseLdsLimit);
@@ -1202,7 +1202,7 @@ int df_train_create_opt(df_train** out, df_chain* c, const df_opt_rule* rules, i
             df_train_destroy(t);
             return hip_err(e, "hipFuncSetAttribute(layer-wise training)");
         }
-        t->lgrid = std::max(1, c->n_cu);
+        t->lgrid = std::max(1, c->grid_cus);
         t->grid = t->lgrid;  // partial rows
         t->fmode = fmode_eligible(t);
         // an explicit form the chain cannot take: the H0-free sweep's shape, or kept
@@ -1215,6 +1215,9 @@ int df_train_create_opt(df_train** out, df_chain* c, const df_opt_rule* rules, i
                                                    : "DF_SWEEP_KEPT needs a chain on the generic or wide kernel");
         }
     }
+    if (c->debug_launch)  // tuning aid (DF_DEBUG_LAUNCH=1): the resident grids on stderr
+        std::fprintf(stderr, "[df] train: %s sweep, %d CUs (of %d), grid %d at %d workgroups per CU, lgrid %d\n",
+                     t->layerwise ? "layer-wise" : "fused", c->grid_cus, c->n_cu, t->grid, occ, t->lgrid);
     const size_t pb = sizeof(float) * (size_t)std::max<int64_t>(t->P, 4);
     if (t->d_params.alloc(pb) != hipSuccess || t->d_m.alloc(pb) != hipSuccess || t->d_v.alloc(pb) != hipSuccess ||
         t->d_grad.alloc(pb) != hipSuccess || t->d_partial.alloc(pb * t->grid) != hipSuccess ||
@@ -1470,7 +1473,7 @@ int df_train_logpdf_grad(df_train* t, const float* x, const float* theta, float*
             plan.push_back(so);
         }
         t->score_ops.swap(plan);
-        t->score_grid = std::max(1, c->n_cu * std::max(1, occ));
+        t->score_grid = std::max(1, c->grid_cus * std::max(1, occ));
         if (c->debug_launch)
             std::fprintf(stderr, "[df] logpdf_grad: %zu launches (%s), %d workgroups of %d waves per CU, grid %d\n",
                          t->score_ops.size(), t->score_per_net ? "per net" : "per layer", occ, kScoreWaves,

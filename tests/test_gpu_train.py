@@ -19,11 +19,9 @@ from densityflows_amd.train import Adam, HIPTrainer, load_trainables, setup, tra
 import densityflows_amd.train as train_mod
 from helpers import _single_dense_spec, random_net, close, spec_to_element
 from oracle import flow_oracle as O
+from train_edge_cases import (G_ATOL, G_RTOL, SPECS, _flat_oracle_grads, _inputs, _tensor_slices)
 
 pytestmark = pytest.mark.gpu
-
-G_RTOL = 1e-4
-G_ATOL = 2e-5
 
 
 def _dev(a, dev):
@@ -32,91 +30,6 @@ def _dev(a, dev):
 
     a = np.asarray(a, np.float32)
     return torch.from_numpy(np.ascontiguousarray(a.T).ravel()).to(dev)
-
-
-def _flat_oracle_grads(spec, grads):
-    parts = []
-    for L, g in zip(O._flat_layers(spec), grads):
-        if L["kind"] == "norm":
-            continue
-        for net in ("s_net", "t_net"):
-            if net not in L:
-                continue
-            for (dW, db), D in zip(g[net], L[net]):
-                parts.append(np.asarray(dW).ravel(order="F"))
-                if D.get("b") is not None:
-                    parts.append(np.asarray(db))
-    return np.concatenate(parts)
-
-
-def _tensor_slices(spec):
-    out, o = [], 0
-    for L in O._flat_layers(spec):
-        if L["kind"] == "norm":
-            continue
-        for net in ("s_net", "t_net"):
-            for D in L.get(net, []):
-                out.append(slice(o, o + D["W"].size))
-                o += D["W"].size
-                if D.get("b") is not None:
-                    out.append(slice(o, o + D["b"].size))
-                    o += D["b"].size
-    return out
-
-
-def _readme_spec(rng, hidden=16):
-    """test/runtests.jl:103-109: three RNVP layers + NormalizationLayer(x, -1, 1)."""
-    layers = [O.rnvp_layer(rng, O.coupling_axes(5, m, n=1), hidden=hidden, bias_scale=0.1, out_scale=0.5)
-              for m in ([1, 2, 3], [3, 4, 5], [5, 1, 2])]
-    layers.append({"kind": "norm", "x_min": np.full(5, -3.0, np.float32), "x_max": np.full(5, 2.5, np.float32),
-                   "alpha": -1.0, "beta": 1.0})
-    return {"kind": "chain", "layers": layers}
-
-
-def _cfg2_spec(rng):
-    """BASELINE configs[1]: FlowChain(CouplingBlock, 4, 5; hidden 64), n = 0."""
-    blocks = []
-    for _ in range(4):
-        blocks.append(O.coupling_block(rng, O.coupling_axes_cut(5, n=0), hidden=64, bias_scale=0.1,
-                                       out_scale=0.1))
-    return {"kind": "chain", "layers": blocks}
-
-
-def _mixed_spec(rng):
-    """tanh / sigmoid conditioners, n_sublayers = 1, a NICE layer, hidden 32."""
-    nice = O.rnvp_layer(rng, O.coupling_axes(6, [2, 5], n=2), hidden=32, act="tanh", bias_scale=0.1)
-    nice["kind"] = "nice"
-    del nice["s_net"]
-    return {"kind": "chain", "layers": [
-        O.rnvp_layer(rng, O.coupling_axes(6, [1, 3, 6], n=2), hidden=32, act="tanh", bias_scale=0.1,
-                     out_scale=0.5),
-        nice,
-        O.coupling_block(rng, O.coupling_axes_cut(6, 2, n=2), n_sub=1, hidden=32, act="sigmoid",
-                         bias_scale=0.1, out_scale=0.5),
-    ]}
-
-
-def _wide_spec(rng):
-    """hidden 256 (the layer-wise path): a conditioned 8-d chain with MFMA-sized
-    outputs (4 transformed dims), a 3-Dense-hidden net and tanh."""
-    return {"kind": "chain", "layers": [
-        O.coupling_block(rng, O.coupling_axes_cut(8, 4, n=3), hidden=256, bias_scale=0.1, out_scale=0.1),
-        O.rnvp_layer(rng, O.coupling_axes(8, [2, 4, 6, 8, 1], n=3), n_sub=3, hidden=128, act="tanh",
-                     bias_scale=0.1, out_scale=0.2),
-        {"kind": "norm", "x_min": np.full(8, -3.0, np.float32), "x_max": np.full(8, 3.5, np.float32),
-         "alpha": 0.0, "beta": 1.0},
-    ]}
-
-
-def _cfg5_spec(rng):
-    """BASELINE configs[3]/[4] model: FlowChain(CouplingBlock, 8, 32; n = 8, hidden 256)."""
-    return {"kind": "chain", "layers": [
-        O.coupling_block(rng, O.coupling_axes_cut(32, n=8), hidden=256, bias_scale=0.1, out_scale=0.1)
-        for _ in range(8)]}
-
-
-SPECS = {"readme": (_readme_spec, 5, 1), "cfg2": (_cfg2_spec, 5, 0), "mixed": (_mixed_spec, 6, 2),
-         "wide": (_wide_spec, 8, 3), "cfg5": (_cfg5_spec, 32, 8)}
 
 
 @pytest.fixture(params=["fused", "layerwise"])
@@ -135,13 +48,6 @@ def _setup(name, seed=0):
     spec = make(rng)
     chain = spec_to_element(spec)
     return spec, chain, d, n
-
-
-def _inputs(d, n, B, seed=1):
-    rng = np.random.default_rng(seed)
-    x = rng.standard_normal((d, B)).astype(np.float32)
-    th = rng.random((n, B)).astype(np.float32) if n > 0 else np.zeros((0, B), np.float32)
-    return x, th
 
 
 def _gpu_grad(tr, x, th, cuda, n_total=None):
@@ -240,34 +146,6 @@ def test_h0_free_sweep_bitwise_equals_kept_h0(cuda, B):
         assert tr.sweep() == want  # after the first gradient: the buffers fitted
     np.testing.assert_array_equal(out[0][0], out[1][0])
     assert out[0][1] == out[1][1]
-
-
-def _cfg5_in40_spec(rng):
-    """config-5-sized nets whose first Dense takes 40 inputs (d = 32, n = 24): the wide
-    SPLIT kernel runs the inverse pass, but the H0-free sweep's 32-float feature rows do
-    not hold them."""
-    return {"kind": "chain", "layers": [
-        O.coupling_block(rng, O.coupling_axes_cut(32, n=24), hidden=256, bias_scale=0.1, out_scale=0.1)
-        for _ in range(2)]}
-
-
-SPECS["cfg5_in40"] = (_cfg5_in40_spec, 32, 24)
-
-
-def _cfg5_in52_spec(rng):
-    """One config-5-sized block whose first Dense takes 52 inputs (d = 16, n = 44: 8 identity
-    dims + 44 conditions, 8 transformed dims, n + d = 60 <= 64): the reverse sweep's x̄ = W0ᵀδ0
-    runs apart from the W1ᵀδ1 launch.  w1t_delta_xbar (df_train_capi.hip) keeps W0ᵀ resident
-    beside the 96 KiB of SPLIT W1ᵀ chunk buffers; with 49-64 inputs W0ᵀ has four 16-row tiles,
-    so its split planes cost 8 · 4 · 3 KiB = 96 KiB and its f32 fragments 4 · 16 · 1 KiB =
-    64 KiB: 96 + 64 KiB (+ 64 B of column table) passes the 160 KiB of LDS, the function
-    returns false, and a plain δ0 launch is followed by an x̄-only product.  (40 inputs: three
-    tiles, 96 + 48 KiB, resident.)"""
-    return {"kind": "chain", "layers": [
-        O.coupling_block(rng, O.coupling_axes_cut(16, n=44), hidden=256, bias_scale=0.1, out_scale=0.1)]}
-
-
-SPECS["cfg5_in52"] = (_cfg5_in52_spec, 16, 44)
 
 
 @pytest.mark.parametrize("name,sweep,want", [
