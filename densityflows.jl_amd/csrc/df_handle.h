@@ -1,6 +1,7 @@
 // df_handle.h — the df_chain handle and the host helpers shared by the C ABI
-// translation units (df_capi.hip: inference entry points, df_train_capi.hip:
-// training entry points).
+// translation units (df_capi.hip: inference entry points; df_train_capi.hip:
+// training entry points, with df_lsweep.hip: the layer-wise reverse sweep; the
+// df_train handle of those two is in df_trainer.h, its host plan in df_train_plan.h).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,5 +1,5 @@
 // df_pack.h — host-only helpers of the weight packers (df_plan.cpp; the fragment walkers
-// also serve the training blobs of df_train_capi.hip): cutting a blob into stages, writing
+// also serve the training blobs of df_train_plan.cpp): cutting a blob into stages, writing
 // a parameter together with its repack pair, and the index nests of the MFMA fragments.
 #pragma once
 

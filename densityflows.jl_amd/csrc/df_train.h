@@ -21,7 +21,7 @@
 
 #include <hip/hip_runtime.h>
 
-#include "df_plan.h"
+#include "df_train_plan.h"
 
 namespace df {
 
@@ -50,40 +50,10 @@ constexpr int train_threads(bool split) { return split ? kTrainThreads / kTrainS
 constexpr int kTS = 20;  // row stride (floats)
 
 namespace trn {
-// Activation modes of the training kernels: σ' from the output alone, relu-only,
-// or σ' of softplus / logcosh / swish, which needs the pre-activation.
-enum { AM_Y = 0, AM_RELU = 1, AM_PRE = 2 };
-
 // σ' applied by the layer-wise δ kernels when the factor was stored at recompute
 // time (nets with a pre-activation σ): hprev then holds σ'(x) itself.
 constexpr int kDactStored = 64;
 }  // namespace trn
-
-// One conditioner net of the specialised shape, as the training kernel sees it.
-struct GNet {
-    UNet u;                  // forward fragments (offsets rebased to the net's own LDS copy)
-    int32_t n_in;            // conditioner inputs (|axis_nn|)
-    int32_t h_true;          // hidden width
-    int32_t off_w0t;         // transposed region: W0ᵀ fragments [kq < HT][lane][4]
-    int32_t off_ht;          // transposed region: W_hᵀ fragments [kq][m][lane][4]
-    int32_t fwd_bytes;       // forward region bytes (16-B multiple)
-    int32_t t_bytes;         // transposed region bytes
-    int64_t fwd_src;         // byte offset of the forward region in the chain blob
-    int64_t t_src;           // byte offset of the transposed region in the training blob
-    int32_t p_begin, p_count;          // the net's contiguous slice of the trainables
-    int32_t w_off[3], b_off[3];        // first Dense, hidden Dense, output Dense (b_off -1: no bias)
-    // SPLIT (chain plan.split, hidden 32/64, relu): the recompute runs on the net's
-    // region of the chain's SPLIT blob (bitwise the inverse pass), W1ᵀδ and dW1 on
-    // bf16x3 products; W1ᵀ planes [c][m][p][lane][8] in the trainer's split blob
-    int32_t split;
-    UNet su;                 // SPLIT forward region offsets (rebased to the net's LDS copy)
-    int32_t sfwd_bytes;
-    int64_t sfwd_src;        // byte offset of the net's region in the chain's SPLIT blob
-    int32_t st_bytes;
-    int64_t st_src;          // byte offset of its W1ᵀ planes in the trainer's split blob
-};
-
-enum : int { TR_PHASE_S = 0, TR_PHASE_T = 1 };
 
 struct TrainArgs {
     const float* u_in;       // U[li+1]: the layer's input in the inverse pass
@@ -127,20 +97,6 @@ hipError_t launch_repack_split(uint8_t* blob, const int32_t* dst, const int32_t*
                                const float* params, hipStream_t st);
 
 // ---- optimiser chains (df_train_create_opt; Optimisers.OptimiserChain) ----
-// The rules of a chain, passed to the kernels by value: kind[r] is a df_opt_kind, p[r] its
-// parameters (df_opt_rule::p).
-constexpr int kOptMaxRules = 8;
-struct OptChain {
-    int32_t n;
-    int32_t kind[kOptMaxRules];
-    float p[kOptMaxRules][4];
-};
-// One 256-thread workgroup of the update kernel: elements [begin, begin + count) of the
-// flat vectors, all of parameter tensor `tensor` (no workgroup spans two tensors).
-struct OptBlock {
-    int32_t begin, count, tensor;
-};
-constexpr int kOptThreads = 256;
 // tensor_sumsq_kernel: the longest chain of additions one element's square goes through.
 // 4 accumulators per thread, each over every 256th quad of the tensor (a tensor has at
 // most 256·256 floats = 16,384 quads: 64 additions), 2 levels to combine the four, and

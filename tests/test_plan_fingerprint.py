@@ -235,13 +235,14 @@ def matrix():
 # building and running the program
 # ---------------------------------------------------------------------------
 
-def compile_program(plan_cpp, exe, sanitize=True):
+def compile_program(plan_cpp, exe, sanitize=True, program="plan_fingerprint.cpp", more=()):
+    """program (of this directory) with plan_cpp and the sources in more."""
     cxx = shutil.which("g++")
     assert cxx, "g++ is needed to build the planner fingerprint"
     flags = (["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan",
               "-static-libubsan"] if sanitize else ["-O2"])   # -O2: the library's own flags (--time)
-    subprocess.run([cxx, "-std=c++17"] + flags + ["-I", os.path.join(ROOT, "include"), "-I", CSRC,
-                    os.path.join(HERE, "plan_fingerprint.cpp"), plan_cpp, "-o", exe], check=True)
+    subprocess.run([cxx, "-std=c++17"] + flags + ["-I", os.path.join(ROOT, "include"), "-I", CSRC, "-I", HERE,
+                    os.path.join(HERE, program), plan_cpp, *more, "-o", exe], check=True)
     return exe
 
 

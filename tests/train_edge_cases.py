@@ -112,7 +112,7 @@ def _cfg5_in40_spec(rng):
 def _cfg5_in52_spec(rng):
     """One config-5-sized block whose first Dense takes 52 inputs (d = 16, n = 44: 8 identity
     dims + 44 conditions, 8 transformed dims, n + d = 60 <= 64): the reverse sweep's x̄ = W0ᵀδ0
-    runs apart from the W1ᵀδ1 launch.  w1t_delta_xbar (df_train_capi.hip) keeps W0ᵀ resident
+    runs apart from the W1ᵀδ1 launch.  w1t_delta_xbar (df_lsweep.hip) keeps W0ᵀ resident
     beside the 96 KiB of SPLIT W1ᵀ chunk buffers; with 49-64 inputs W0ᵀ has four 16-row tiles,
     so its split planes cost 8 · 4 · 3 KiB = 96 KiB and its f32 fragments 4 · 16 · 1 KiB =
     64 KiB: 96 + 64 KiB (+ 64 B of column table) passes the 160 KiB of LDS, the function
