@@ -14,7 +14,8 @@ from .chains import FlowChain, backward, concatenate, forward, forward_, forward
 from .data import (DataArrays, DataPartition, MetaData, dflt_theta, maximum_theta, minimum_theta,
                    normalize_input, resize_output)
 from .flows import (Box, Flow, HalfSpaces, MvNormal, Region, logpdf, logpdf_grad, logpdf_grid, nll_partial_sum, pdf,
-                    predict, sample, sample_with_rejection, training_loss, validation_loss)
+                    pdf_marginals, predict, sample, sample_with_rejection, training_loss, trapezoid_weights,
+                    validation_loss)
 from .layers import (Chain, CouplingBlock, CouplingLayer, Dense, FlowElement, NICECouplingLayer,
                      NormalizationLayer, RNVPCouplingLayer, default_net)
 from .train import (Adam, AdamW, ClipGrad, ClipNorm, Descent, OptimiserChain, TrainState, WeightDecay, adjust_,

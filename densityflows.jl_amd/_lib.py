@@ -191,6 +191,8 @@ SIGNATURES = {
     "df_flow_sample_region": (C.c_int, [_VP, _VP, _VP, _I64, C.POINTER(df_region), _I64, _I64, C.c_uint64,
                                         C.c_uint64, C.POINTER(_I64), C.POINTER(_I64), _VP]),
     "df_flow_logpdf_grid": (C.c_int, [_VP, _VP, C.POINTER(_I64), _I64, _I64, _VP, _I64, _VP]),
+    "df_flow_pdf_marginals": (C.c_int, [_VP, _VP, _VP, C.POINTER(_I64), _I64, _I64, C.POINTER(C.c_int32), C.c_int32,
+                                        _VP, _I64, _VP]),
     "df_theta_broadcast": (C.c_int, [_VP, _VP, C.c_int, _I64, _VP]),
     "df_chain_clock_probe": (C.c_int, [_VP, C.c_int]),
     "df_chain_clock_read": (C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_I64)]),

@@ -14,7 +14,8 @@ from .data import DataArrays, MetaData, maximum_theta, minimum_theta
 from .hip import as_julia_device, julia_empty
 
 __all__ = ["Flow", "MvNormal", "predict", "sample", "sample_with_rejection", "Box", "HalfSpaces", "Region",
-           "logpdf", "logpdf_grid", "logpdf_grad", "pdf", "training_loss", "validation_loss", "nll_partial_sum"]
+           "logpdf", "logpdf_grid", "logpdf_grad", "pdf", "pdf_marginals", "trapezoid_weights", "training_loss",
+           "validation_loss", "nll_partial_sum"]
 
 LOG2PI = float(np.log(2.0 * np.pi))
 
@@ -376,9 +377,9 @@ def _axis_values(a, what):
     return a, False
 
 
-def _grid_eval(flow: Flow, x_axes, theta_axes, first, count, chunk):
-    """Shared by logpdf_grid and the tuple-x logpdf → (flat device values, lens, numpy out?,
-    whole grid?)."""
+def _grid_axes(flow: Flow, x_axes, theta_axes):
+    """The d + n axes of a grid → (handle, axis vectors, lens, any device tensor?, the axes
+    concatenated on the device)."""
     import torch
 
     h = flow.hip()
@@ -408,14 +409,29 @@ def _grid_eval(flow: Flow, x_axes, theta_axes, first, count, chunk):
                               for v in parts]).contiguous()
     else:
         axes_buf = torch.from_numpy(np.concatenate(parts) if parts else np.zeros(0, np.float32)).to(h.device)
+    return h, parts, lens, any_tensor, axes_buf
+
+
+def _grid_window(lens, first, count):
+    """(first, count) of a window of the grid, checked; count None: to the end."""
     P = 1
     for L in lens:
         P *= L
-    whole = first == 0 and count is None
     first = int(first)
     count = P - first if count is None else int(count)
     if first < 0 or count < 0 or first + count > P:
         raise _lib.DimensionMismatch(f"window [{first}, {first + count}) outside the grid of {P} points")
+    return first, count
+
+
+def _grid_eval(flow: Flow, x_axes, theta_axes, first, count, chunk):
+    """Shared by logpdf_grid and the tuple-x logpdf → (flat device values, lens, numpy out?,
+    whole grid?)."""
+    import torch
+
+    h, _, lens, any_tensor, axes_buf = _grid_axes(flow, x_axes, theta_axes)
+    whole = first == 0 and count is None
+    first, count = _grid_window(lens, first, count)
     lpb = torch.empty(count, dtype=torch.float32, device=h.device)
     with torch.cuda.device(h.device):
         h.run_logpdf_grid(axes_buf, lens, first, count, lpb, chunk)
@@ -438,6 +454,94 @@ def logpdf_grid(flow: Flow, x_axes, theta_axes=None, first: int = 0, count: Opti
     lpb, lens, was_np, whole = _grid_eval(flow, x_axes, theta_axes, first, count, chunk)
     v = HIPChain._ldj_view(lpb, lens) if whole else lpb
     return _to_numpy(v) if was_np else v
+
+
+MAX_MARGINALS = 128     # requests of one df_flow_pdf_marginals call
+
+
+def trapezoid_weights(axis) -> np.ndarray:
+    """Trapezoid-rule weights of one axis in float64, from its float32 values: half the end
+    interval at the ends, half the distance between the neighbours inside, so that
+    ``weights @ f`` is ``numpy.trapz(f, axis)``.  An axis of one value has weight 1 (a slice)."""
+    a = np.asarray(axis, dtype=np.float32).astype(np.float64)
+    if a.ndim != 1:
+        raise _lib.DimensionMismatch(f"an axis must be a vector, got size {a.shape}")
+    if a.size <= 1:
+        return np.ones(a.size, np.float64)
+    w = np.empty(a.size, np.float64)
+    w[0] = 0.5 * (a[1] - a[0])
+    w[-1] = 0.5 * (a[-1] - a[-2])
+    w[1:-1] = 0.5 * (a[2:] - a[:-2])
+    return w
+
+
+def _marginal_requests(keep, lens, d):
+    """``keep`` → sorted, distinct tuples of ascending axis numbers."""
+    na = len(lens)
+    if keep is None:
+        xs = [k for k in range(d) if lens[k] > 1]
+        keep = [()] + [(a,) for a in xs] + [(a, b) for i, a in enumerate(xs) for b in xs[i + 1:]]
+    out = set()
+    for K in keep:
+        K = (int(K),) if np.ndim(K) == 0 else tuple(int(v) for v in K)
+        if len(K) > 2:
+            raise _lib.UnsupportedError(f"a marginal keeps at most two axes, got {K}")
+        if len(set(K)) != len(K) or any(v < 0 or v >= na for v in K):
+            raise _lib.ArgumentError(f"kept axes must be distinct and in [0, {na}), got {K}")
+        out.add(tuple(sorted(K)))
+    out = sorted(out, key=lambda K: (len(K), K))
+    if len(out) > MAX_MARGINALS:
+        raise _lib.UnsupportedError(f"at most {MAX_MARGINALS} marginal tables per call, got {len(out)}")
+    return out
+
+
+def pdf_marginals(flow: Flow, x_axes, theta=None, keep=None, weights="trapezoid", first: int = 0,
+                  count: Optional[int] = None, chunk: int = 0):
+    """Marginal tables of ``pdf`` on the grid of :func:`logpdf_grid`, reduced on the device
+    (one library call, ``df_flow_pdf_marginals``): only the tables come back, whatever the
+    grid's size.  ``theta``: n entries, values or vectors, as ``theta_axes`` there.
+
+    ``keep``: the tables wanted, each a tuple of 0, 1 or 2 axis numbers (x axes 0 … d-1, then
+    the θ axes); every other axis is integrated with its quadrature weights.  ``None`` is the
+    corner plot: ``()`` (the total mass), every x axis of more than one value, every pair of
+    them.  ``weights``: ``"trapezoid"`` (:func:`trapezoid_weights` of every axis), ``"sum"``
+    (all 1) or a tuple of d + n vectors, the caller's own rule.  ``first`` / ``count``: the
+    sums over a window of the grid's points only; windows add up.
+
+    Returns ``{(): scalar, (a,): (L_a,), (a, b): (L_a, L_b)}`` in float64, keys sorted; numpy
+    in, numpy out (Fortran-ordered), any device tensor among the axes gives device tensors.
+    The sums are accumulated with atomic adds: two runs may differ in the last bits."""
+    import torch
+
+    h, parts, lens, any_tensor, axes_buf = _grid_axes(flow, x_axes, theta)
+    reqs = _marginal_requests(keep, lens, flow.d)
+    first, count = _grid_window(lens, first, count)
+    if isinstance(weights, str):
+        if weights not in ("trapezoid", "sum"):
+            raise _lib.ArgumentError(f'weights must be "trapezoid", "sum" or a tuple of vectors, got {weights!r}')
+        host = [v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v for v in parts]
+        wparts = [trapezoid_weights(v) if weights == "trapezoid" else np.ones(v.shape[0], np.float64) for v in host]
+    else:
+        wparts = [np.atleast_1d(np.asarray(w.detach().cpu().numpy() if isinstance(w, torch.Tensor) else w,
+                                           dtype=np.float64)) for w in tuple(weights)]
+        if len(wparts) != len(lens) or any(w.ndim != 1 or w.shape[0] != L for w, L in zip(wparts, lens)):
+            raise _lib.DimensionMismatch(f"weights must be d + n = {len(lens)} vectors of the axes' lengths {lens}")
+    wbuf = torch.from_numpy(np.concatenate(wparts) if wparts else np.zeros(0, np.float64)).to(h.device)
+    shapes = [tuple(lens[k] for k in K) for K in reqs]
+    sizes = [int(np.prod(s, dtype=np.int64)) for s in shapes]
+    out = torch.empty(sum(sizes), dtype=torch.float64, device=h.device)
+    with torch.cuda.device(h.device):
+        h.run_pdf_marginals(axes_buf, wbuf, lens, first, count, reqs, out, chunk)
+    res, at = {}, 0
+    flat = out if any_tensor else out.cpu().numpy()
+    for K, shape, size in zip(reqs, shapes, sizes):
+        t = flat[at:at + size]
+        at += size
+        if any_tensor:
+            res[K] = t.reshape(tuple(reversed(shape))).permute(tuple(reversed(range(len(shape)))))
+        else:
+            res[K] = np.array(t.reshape(shape, order="F"), order="F")
+    return res
 
 
 def _logpdf_axes(flow: Flow, x: tuple, theta):

@@ -277,6 +277,23 @@ class HIPChain:
                                                 C.c_int64(count), _ptr(lpbuf), C.c_int64(chunk),
                                                 _stream(self.device)), "logpdf_grid")
 
+    def run_pdf_marginals(self, axes_buf, weights_buf, lens, first: int, count: int, keep, outbuf, chunk: int = 0):
+        """df_flow_pdf_marginals: the marginal tables of pdf over points [first, first + count)
+        of the grid of ``run_logpdf_grid``, into the float64 device buffer ``outbuf`` one after
+        the other.  ``weights_buf``: float64, laid out like ``axes_buf``.  ``keep``: one tuple
+        of 0, 1 or 2 ascending axis numbers per table."""
+        if len(lens) != self.d + self.n:
+            raise _lib.DimensionMismatch(f"a grid needs d + n = {self.d + self.n} axis lengths, got {len(lens)}")
+        if any(len(k) > 2 for k in keep):
+            raise _lib.UnsupportedError("a marginal keeps at most two axes")
+        arr = (C.c_int64 * max(len(lens), 1))(*[int(v) for v in lens])
+        flat = [int(v) for k in keep for v in (tuple(k) + (-1, -1))[:2]]
+        req = (C.c_int32 * max(len(flat), 1))(*flat)
+        _lib.check(self.lib.df_flow_pdf_marginals(self.handle, _ptr(axes_buf), _ptr(weights_buf), arr,
+                                                  C.c_int64(first), C.c_int64(count), req, C.c_int32(len(keep)),
+                                                  _ptr(outbuf), C.c_int64(chunk), _stream(self.device)),
+                   "pdf_marginals")
+
     def run_theta_broadcast(self, outbuf, thvec, batch: int):
         """df_theta_broadcast: the n-vector ``thvec`` into every column of the (n, batch) ``outbuf``."""
         _lib.check(self.lib.df_theta_broadcast(_ptr(outbuf), _ptr(thvec), C.c_int(int(thvec.numel())),

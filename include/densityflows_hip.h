@@ -244,6 +244,33 @@ int df_random_normal(float* out, int64_t count, uint64_t seed, uint64_t offset, 
 int df_flow_logpdf_grid(df_chain* chain, const float* axes, const int64_t* lens, int64_t first, int64_t count,
                         float* logpdf_out, int64_t chunk, void* stream);
 
+/* ---- marginal densities over grid axes (additive to ABI 5) --------------------
+ * The 0-, 1- and 2-D marginal tables of pdf on the grid of df_flow_logpdf_grid, reduced on
+ * the device chunk by chunk: nothing of the grid's size is written anywhere.
+ * axes, lens, first, count, chunk, stream: as for df_flow_logpdf_grid.  weights: DEVICE,
+ * one double per axis value, laid out like `axes` (quadrature weights, the caller's rule).
+ * keep: HOST, n_marg requests of two int32 each, the kept axes in ascending order, -1 for
+ * an unused slot: {-1,-1} the total mass, {a,-1} a 1-D table, {a,b} with a < b a 2-D one.
+ * For request K
+ *   m_K[i_K] = sum over the window's points p with kept indices i_K of
+ *              exp(logpdf(p)) * prod over k not in K of w_k[i_k(p)]
+ * with logpdf(p) bitwise df_flow_logpdf_grid's value, exp taken in double of that float,
+ * products and sums in double.  Kept axes may be θ axes.
+ * out: DEVICE doubles, table j behind the tables before it: 1, L_a or L_a * L_b values,
+ * the lower-numbered kept axis fastest.  The call zeroes the tables on the stream and
+ * then adds the window's sums: results of several windows (calls, devices) add up.
+ * Sums are accumulated with floating-point atomic adds: two runs may differ in the last
+ * bits.  No host synchronisation; the staging buffer of df_flow_logpdf_grid is used,
+ * one chunk of floats larger, under the same growth rules.
+ * count == 0: DF_OK, tables zeroed, nothing launched.  n_marg == 0: DF_OK, nothing runs.
+ * DF_ERR_INVALID: a null chain, lens, keep or out (n_marg > 0), null axes or weights
+ * (count > 0), a kept index outside [0, d + n), not ascending or repeated.
+ * DF_ERR_SHAPE: as df_flow_logpdf_grid, or a total table size past int64.
+ * DF_ERR_UNSUPPORTED: more than 128 requests. */
+int df_flow_pdf_marginals(df_chain* chain, const float* axes, const double* weights, const int64_t* lens,
+                          int64_t first, int64_t count, const int32_t* keep, int32_t n_marg, double* out,
+                          int64_t chunk, void* stream);
+
 /* out (n, batch) = the n-vector theta in every column, on the device: the NTuple θ of
  * logpdf(flow, x, θ::Tuple) (src/Flows.jl:284, collect(θ) broadcast over the points). */
 int df_theta_broadcast(float* out, const float* theta, int n, int64_t batch, void* stream);
