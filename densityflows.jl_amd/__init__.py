@@ -19,7 +19,7 @@ from .flows import (Box, Flow, HalfSpaces, MvNormal, Region, logpdf, logpdf_grad
 from .layers import (Chain, CouplingBlock, CouplingLayer, Dense, FlowElement, NICECouplingLayer,
                      NormalizationLayer, RNVPCouplingLayer, default_net)
 from .train import (Adam, AdamW, ClipGrad, ClipNorm, Descent, OptimiserChain, TrainState, WeightDecay, adjust_,
-                    load_trainables, setup, train_, trainables)
+                    check_weights, load_trainables, setup, train_, trainables, weighted_nll)
 
 __version__ = "0.1.0"
 

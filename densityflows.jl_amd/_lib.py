@@ -167,6 +167,13 @@ SIGNATURES = {
     "df_train_step_graph": (C.c_int, [_VP, _VP, _VP, _I64, _I64, _VP, _VP]),
     "df_batch_gather": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, _I64, _VP, _I64, _I64, _VP]),
     "df_train_epoch": (C.c_int, [_VP, _VP, _VP, _I64, _VP, _I64, _VP, C.POINTER(_I64), _VP]),
+    "df_train_gradient_w": (C.c_int, [_VP, _VP, _VP, _VP, _I64, C.c_double, _VP, _VP]),
+    "df_train_step_w": (C.c_int, [_VP, _VP, _VP, _VP, _I64, _VP, _VP]),
+    "df_train_step_graph_w": (C.c_int, [_VP, _VP, _VP, _VP, _I64, C.c_double, _VP, _VP]),
+    "df_batch_gather_w": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, _I64, _VP, _I64, _I64, _VP]),
+    "df_train_epoch_w": (C.c_int, [_VP, _VP, _VP, _VP, _I64, _VP, _I64, _VP, C.POINTER(_I64), _VP]),
+    "df_flow_logpdf_wsum": (C.c_int, [_VP, _VP, _VP, _VP, _I64, _VP, _VP]),
+    "df_chain_logpdf_wsum": (C.c_int, [_VP, _VP, _VP, _VP, _I64, _VP, _VP]),
     "df_train_get_params": (C.c_int, [_VP, _FP, _I64]),
     "df_train_set_params": (C.c_int, [_VP, _FP, _I64]),
     "df_train_set_debug": (C.c_int, [_VP, C.c_int]),

@@ -52,6 +52,36 @@ batch_gather_kernel(float* __restrict__ x_out, float* __restrict__ th_out, const
         th_out[q] = th_set[row * n + r];
 }
 
+// The same gather with a third array, the sample weights: w_out[j] = w_set[row j], by the
+// threads past the x and θ elements.  The same rule for a bad position or index (row 0).
+__global__ void __launch_bounds__(kGatherThreads)
+batch_gather_w_kernel(float* __restrict__ x_out, float* __restrict__ th_out, float* __restrict__ w_out,
+                      const float* __restrict__ x_set, const float* __restrict__ th_set,
+                      const float* __restrict__ w_set, int d, int n, int64_t n_samples,
+                      const int32_t* __restrict__ order, int64_t first, const int64_t* __restrict__ cursor,
+                      int64_t batchsize, int64_t count) {
+    const int64_t e = (int64_t)blockIdx.x * kGatherThreads + threadIdx.x;
+    const int64_t nx = count * d, nt = count * n;
+    if (e >= nx + nt + count) return;
+    const int which = e < nx ? 0 : (e < nx + nt ? 1 : 2);
+    const int64_t q = which == 0 ? e : (which == 1 ? e - nx : e - nx - nt);
+    const int w = which == 0 ? d : (which == 1 ? n : 1);
+    const int64_t j = q / w;
+    const int r = (int)(q - j * w);
+    const int64_t pos = first + (cursor ? *cursor * batchsize : 0) + j;
+    int64_t row = 0;
+    if ((uint64_t)pos < (uint64_t)n_samples) {
+        row = order ? (int64_t)order[pos] : pos;
+        if ((uint64_t)row >= (uint64_t)n_samples) row = 0;
+    }
+    if (which == 0)
+        x_out[q] = x_set[row * d + r];
+    else if (which == 1)
+        th_out[q] = th_set[row * n + r];
+    else
+        w_out[q] = w_set[row];
+}
+
 // *bad = the number of entries of order[0, n_samples) outside [0, n_samples); *bad is zeroed
 // by the launcher.  A valid order adds nothing.
 __global__ void __launch_bounds__(kGatherThreads)
@@ -71,6 +101,35 @@ __global__ void cursor_advance_kernel(int64_t* cursor, const double* lp, double*
         if (step_lp) step_lp[c] = *lp;
         *cursor = c + 1;
     }
+}
+
+// The weighted step's end: both of its sums to step_ws[2·*cursor], then the cursor moves on.
+__global__ void cursor_advance_w_kernel(int64_t* cursor, const double* ws, double* step_ws) {
+    if (threadIdx.x == 0) {
+        const int64_t c = *cursor;
+        if (step_ws) {
+            step_ws[2 * c] = ws[0];
+            step_ws[2 * c + 1] = ws[1];
+        }
+        *cursor = c + 1;
+    }
+}
+
+hipError_t launch_batch_gather_w(float* x_out, float* th_out, float* w_out, const float* x_set, const float* th_set,
+                                 const float* w_set, int d, int n, int64_t n_samples, const int32_t* order,
+                                 int64_t first, const int64_t* cursor, int64_t batchsize, int64_t count,
+                                 hipStream_t st) {
+    if (!th_out || !th_set) n = 0;
+    const int64_t total = count * ((int64_t)d + n + 1);
+    if (total <= 0) return hipSuccess;
+    hipLaunchKernelGGL(batch_gather_w_kernel, dim3(gather_blocks(total)), dim3(kGatherThreads), 0, st, x_out, th_out,
+                       w_out, x_set, th_set, w_set, d, n, n_samples, order, first, cursor, batchsize, count);
+    return hipGetLastError();
+}
+
+hipError_t launch_cursor_advance_w(int64_t* cursor, const double* ws, double* step_ws, hipStream_t st) {
+    hipLaunchKernelGGL(cursor_advance_w_kernel, dim3(1), dim3(64), 0, st, cursor, ws, step_ws);
+    return hipGetLastError();
 }
 
 hipError_t launch_batch_gather(float* x_out, float* th_out, const float* x_set, const float* th_set, int d, int n,

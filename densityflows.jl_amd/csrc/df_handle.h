@@ -139,6 +139,10 @@ struct df_chain {
     DevBuf d_rej_cnt;     // int64 [accepted | tried | round base | -]
     int64_t rej_cap = 0;  // candidates
     std::vector<float> h_rej_region;  // the host block d_rej_region was last uploaded from
+    // workspace of df_flow_logpdf_wsum / df_chain_logpdf_wsum: the per-sample logpdf (float
+    // [wlp_cap]) and the span sums of the fp64 reductions; they only grow
+    DevBuf d_wlp, d_wlp_part;
+    int64_t wlp_cap = 0;
     ~df_chain() {
         if (d_theta_ws) (void)hipFree(d_theta_ws);
     }

@@ -64,6 +64,7 @@ struct LSweep {
     const uint8_t* lsb;       // its SPLIT planes
     bool lsplit;              // the chain's arithmetic, fixed at df_chain_create
     bool fm;                  // H0-free sweep (struct df_train)
+    const float* wj;          // weighted loss: j̄ per sample (nullptr: inv_n)
     int par = 0;              // buffer parity of the current net
     bool front_done = false;  // this net's couple_bwd ran in the previous merged launch
     int rc = DF_OK;           // the first error: nothing launches after it
@@ -137,6 +138,7 @@ struct LSweep {
         b.zbar = t->bb.d_zbar.as<float>();
         b.ebuf = t->bb.d_ebuf.as<float>();
         b.inv_n = inv_n;
+        b.wj = wj;
         b.ld_in = b.ld_out = b.ld_h = b.ld_x = t->tp.lwidth;
         return b;
     }
@@ -402,14 +404,15 @@ hipError_t lsweep_set_lds_limits() {
 }
 
 // Reverse sweep of the layer-wise path (chain order; see df_ltrain.h).
-int lsweep(df_train* t, const float* x, const float* theta, int64_t batch, float inv_n, bool flow, hipStream_t st) {
+int lsweep(df_train* t, const float* x, const float* theta, int64_t batch, float inv_n, const float* wj, bool flow,
+           hipStream_t st) {
     df_chain* c = t->c;
     const int64_t ntiles = (batch + 15) / 16;
     const unsigned dgrid =
         (unsigned)std::max<int64_t>(1, std::min<int64_t>(c->grid_cus, (ntiles + kWavesPerBlock * kLTiles - 1) /
                                                                               (kWavesPerBlock * kLTiles)));
     LSweep s{t, c, x, theta, batch, inv_n, flow, st, dgrid, t->d_lblob.as<const uint8_t>(),
-             t->d_lblob.as<const float>(), t->d_lsblob.as<const uint8_t>(), !c->exact, h0free(t)};
+             t->d_lblob.as<const float>(), t->d_lsblob.as<const uint8_t>(), !c->exact, h0free(t), wj};
     for (size_t oi = 0; oi < t->tp.ops.size() && s.rc == DF_OK; ++oi) {
         const SweepOp& op = t->tp.ops[oi];
         if (op.net < 0) {

@@ -100,6 +100,9 @@ struct LDenseArgs {
     float* dwo_partial;
     int64_t dwo_p_total;
     int dwo_w_off, dwo_b_off, dwo_m_true, dwo_n_true;
+    // weighted instances (df_train_gradient_w): j̄ of sample s is wj[s] = w_s / W, not inv_n;
+    // nullptr selects the unweighted instance at every launch
+    const float* wj;
 };
 
 struct LdwArgs {

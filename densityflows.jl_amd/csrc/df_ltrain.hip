@@ -65,7 +65,8 @@ __device__ __forceinline__ float gather_feature(const LDenseArgs& a, int slot, i
 // ones kSplitWaves × kSplitTiles — one wave per SIMD whose 4 × 16 accumulator tiles sit
 // in the AGPR half of the register file, so every bf16x3 weight fragment read from LDS
 // feeds 4 tiles' products instead of 2 (same samples per workgroup round).
-template <int MT, int IN, int EPI, bool SPLIT = false, int NW = kWavesPerBlock, int TT = kLTiles>
+// WT: the weighted loss, j̄ per sample from LDenseArgs::wj (LEPI_COUPLE)
+template <int MT, int IN, int EPI, bool SPLIT = false, int NW = kWavesPerBlock, int TT = kLTiles, bool WT = false>
 __global__ void __launch_bounds__(NW * 64, 1) ldense_kernel(LDenseArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     constexpr int T = TT;
@@ -436,7 +437,8 @@ __global__ void __launch_bounds__(NW * 64, 1) ldense_kernel(LDenseArgs a) {
                                 float dq;
                                 if (a.phase == TR_PHASE_S) {
                                     a.ebuf[s * 32 + row] = expf(-v[q]);
-                                    dq = -zb * a.u_out[s * a.d + dim] + a.inv_n;  // s̄ = -z̄_af·z_af - j̄
+                                    const float jb = WT ? a.wj[s] : a.inv_n;
+                                    dq = -zb * a.u_out[s * a.d + dim] + jb;       // s̄ = -z̄_af·z_af - j̄
                                 } else {
                                     const bool rnvp = (a.kind == DF_LAYER_RNVP);
                                     const float e = rnvp ? a.ebuf[s * 32 + row] : 1.f;
@@ -492,7 +494,7 @@ size_t front_dwo_lds_bytes(int ht) {
     return tr > red ? tr : red;
 }
 
-template <int HT, int MTO>
+template <int HT, int MTO, bool WT = false>
 __device__ __forceinline__ void couple_body(const LDenseArgs& a, uint8_t* smem, int bid, int nb) {
     uint8_t* wo = smem;                         // W_out: [kq < HT][m < MTO]
     uint8_t* wt = smem + HT * MTO * 1024;       // W_outᵀ: [kq < MTO][m < HT]
@@ -549,9 +551,11 @@ __device__ __forceinline__ void couple_body(const LDenseArgs& a, uint8_t* smem, 
     }
     auto dimq = [&](int m, int q) { return (int)((dimw[m] >> (8 * q)) & 0xffu); };
     float zbn[MTO][4], oun[MTO][4];
+    float jbn = a.inv_n;  // j̄ of this lane's sample (WT: loaded with the pullback's operands)
     auto load_p = [&](int64_t tile) {
         int64_t sl = tile * 16 + j;
         sl = sl < a.batch ? sl : a.batch - 1;
+        if constexpr (WT) jbn = sph ? a.wj[sl] : 0.f;
 #pragma unroll
         for (int m = 0; m < MTO; ++m)
 #pragma unroll
@@ -616,7 +620,7 @@ __device__ __forceinline__ void couple_body(const LDenseArgs& a, uint8_t* smem, 
                     float dq;
                     if (sph) {
                         a.ebuf[s * 32 + row] = expf(-v[q]);
-                        dq = -zb * oun[m][q] + a.inv_n;                 // s̄ = -z̄_af·z_af - j̄
+                        dq = -zb * oun[m][q] + jbn;                     // s̄ = -z̄_af·z_af - j̄
                     } else {
                         const float e = oun[m][q];                     // exp(-s) (RNVP) or 1 (NICE)
                         dq = -zb * e;                                   // t̄ = -z̄_af·exp(-s)
@@ -734,25 +738,28 @@ __device__ __forceinline__ void couple_body(const LDenseArgs& a, uint8_t* smem, 
     }
 }
 
-template <int HT, int MTO>
+template <int HT, int MTO, bool WT = false>
 __global__ void __launch_bounds__(kBlockThreads, 1) couple_bwd_kernel(LDenseArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    couple_body<HT, MTO>(a, smem, blockIdx.x, gridDim.x);
+    couple_body<HT, MTO, WT>(a, smem, blockIdx.x, gridDim.x);
 }
 
-template <int MTO>
+template <int MTO, bool WT>
 void* couple_bwd_ptr_m(int ht) {
     switch (ht) {
-        case 1: return reinterpret_cast<void*>(&couple_bwd_kernel<1, MTO>);
-        case 2: return reinterpret_cast<void*>(&couple_bwd_kernel<2, MTO>);
-        case 4: return reinterpret_cast<void*>(&couple_bwd_kernel<4, MTO>);
-        case 8: return reinterpret_cast<void*>(&couple_bwd_kernel<8, MTO>);
-        case 16: return reinterpret_cast<void*>(&couple_bwd_kernel<16, MTO>);
+        case 1: return reinterpret_cast<void*>(&couple_bwd_kernel<1, MTO, WT>);
+        case 2: return reinterpret_cast<void*>(&couple_bwd_kernel<2, MTO, WT>);
+        case 4: return reinterpret_cast<void*>(&couple_bwd_kernel<4, MTO, WT>);
+        case 8: return reinterpret_cast<void*>(&couple_bwd_kernel<8, MTO, WT>);
+        case 16: return reinterpret_cast<void*>(&couple_bwd_kernel<16, MTO, WT>);
         default: return nullptr;
     }
 }
 
-void* couple_bwd_ptr(int ht, int mto) { return mto == 2 ? couple_bwd_ptr_m<2>(ht) : couple_bwd_ptr_m<1>(ht); }
+void* couple_bwd_ptr(int ht, int mto, bool wt = false) {
+    if (wt) return mto == 2 ? couple_bwd_ptr_m<2, true>(ht) : couple_bwd_ptr_m<1, true>(ht);
+    return mto == 2 ? couple_bwd_ptr_m<2, false>(ht) : couple_bwd_ptr_m<1, false>(ht);
+}
 
 // dW = δ · inᵀ and db = Σ δ over this workgroup's contiguous sample range.
 // Both operands are staged sample-major in LDS (row stride ≡ 4 mod 8 floats:
@@ -1323,13 +1330,13 @@ __global__ void __launch_bounds__(kBlockThreads, 1) ldw_kernel(LdwArgs a) {
 // workgroups run the front first, odd ones the dW products first, so the fronts and the
 // narrow products of the two halves of the CUs interleave.  (The split 256×256 dW is
 // its own launch, ldw_split_kernel: one wave per SIMD.)
-template <int HT, int MTO>
+template <int HT, int MTO, bool WT = false>
 __global__ void __launch_bounds__(kBlockThreads, 1) sweep_kernel(SweepJob j) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const bool front_first = HT > 0 && j.has_front && (blockIdx.x & 1) == 0;
     if constexpr (HT > 0) {
         if (front_first) {
-            couple_body<HT, MTO>(j.front, smem, blockIdx.x, gridDim.x);
+            couple_body<HT, MTO, WT>(j.front, smem, blockIdx.x, gridDim.x);
             __syncthreads();
         }
     }
@@ -1341,12 +1348,19 @@ __global__ void __launch_bounds__(kBlockThreads, 1) sweep_kernel(SweepJob j) {
         __syncthreads();
     }
     if constexpr (HT > 0) {
-        if (j.has_front && !front_first) couple_body<HT, MTO>(j.front, smem, blockIdx.x, gridDim.x);
+        if (j.has_front && !front_first) couple_body<HT, MTO, WT>(j.front, smem, blockIdx.x, gridDim.x);
     }
 }
 
-void* sweep_ptr(int ht, int mto) {
-    if (ht == 0) return reinterpret_cast<void*>(&sweep_kernel<0, 1>);
+void* sweep_ptr(int ht, int mto, bool wt = false) {
+    if (ht == 0) return reinterpret_cast<void*>(&sweep_kernel<0, 1>);  // no front: no j̄
+    if (wt) {
+        if (ht == 16) return mto == 2 ? reinterpret_cast<void*>(&sweep_kernel<16, 2, true>)
+                                      : reinterpret_cast<void*>(&sweep_kernel<16, 1, true>);
+        if (ht == 8) return mto == 2 ? reinterpret_cast<void*>(&sweep_kernel<8, 2, true>)
+                                     : reinterpret_cast<void*>(&sweep_kernel<8, 1, true>);
+        return nullptr;
+    }
     if (ht == 16) return mto == 2 ? reinterpret_cast<void*>(&sweep_kernel<16, 2>)
                                   : reinterpret_cast<void*>(&sweep_kernel<16, 1>);
     if (ht == 8) return mto == 2 ? reinterpret_cast<void*>(&sweep_kernel<8, 2>)
@@ -1366,6 +1380,23 @@ __global__ void gather_features_kernel(LDenseArgs a, int rows) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) v[q] = (f0 + q < a.n_in) ? gather_feature(a, a.feat[f0 + q], s) : 0.f;
     *reinterpret_cast<f32x4*>(a.xsave + (int64_t)s * a.ld_x + f0) = v;
+}
+
+template <int MT>
+void* ldense_couple_w_ptr() {
+    return reinterpret_cast<void*>(&ldense_kernel<MT, LIN_BUF, LEPI_COUPLE, false, kWavesPerBlock, kLTiles, true>);
+}
+
+// the weighted LEPI_COUPLE instances
+void* ldense_ptr_w(int mt) {
+    switch (mt) {
+        case 1: return ldense_couple_w_ptr<1>();
+        case 2: return ldense_couple_w_ptr<2>();
+        case 4: return ldense_couple_w_ptr<4>();
+        case 8: return ldense_couple_w_ptr<8>();
+        case 16: return ldense_couple_w_ptr<16>();
+        default: return nullptr;
+    }
 }
 
 template <int MT>
@@ -1408,7 +1439,8 @@ bool ldense_split_supported(int mt, int in_kind, int epi) { return ldense_ptr(mt
 
 hipError_t launch_ldense(int mt, int in_kind, int epi, const LDenseArgs& a, unsigned grid, size_t lds,
                          hipStream_t st) {
-    void* k = ldense_ptr(mt, in_kind, epi, a.sfrag != nullptr);
+    const bool wt = a.wj && epi == LEPI_COUPLE && in_kind == LIN_BUF && !a.sfrag;
+    void* k = wt ? ldense_ptr_w(mt) : ldense_ptr(mt, in_kind, epi, a.sfrag != nullptr);
     if (!k) return hipErrorInvalidValue;
     void* args[] = {const_cast<LDenseArgs*>(&a)};
     return hipLaunchKernel(k, dim3(grid), dim3(a.sfrag ? kSplitWaves * 64 : kBlockThreads), args, lds, st);
@@ -1429,6 +1461,8 @@ hipError_t set_ldense_lds_limit(size_t lds) {
         }
         hipError_t e = hipFuncSetAttribute(ldense_ptr(mt, LIN_GATHER, LEPI_ACT),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute(ldense_ptr_w(mt), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
     for (int epi : {LEPI_DACT, LEPI_DACT_XBAR, LEPI_DACT_XBAR_MASK}) {
@@ -1453,19 +1487,20 @@ bool front_dwo(int mto) { return mto == 1 && DF_FRONT_DWO; }
 size_t front_dwo_lds(int ht) { return front_dwo_lds_bytes(ht); }
 
 hipError_t launch_couple_bwd(int ht, int mto, const LDenseArgs& a, unsigned grid, size_t lds, hipStream_t st) {
-    void* k = couple_bwd_ptr(ht, mto);
+    void* k = couple_bwd_ptr(ht, mto, a.wj != nullptr);
     if (!k) return hipErrorInvalidValue;
     void* args[] = {const_cast<LDenseArgs*>(&a)};
     return hipLaunchKernel(k, dim3(grid), dim3(kBlockThreads), args, lds, st);
 }
 
 hipError_t set_couple_bwd_lds_limit(size_t lds) {
-    for (int ht : {1, 2, 4, 8, 16})
-        for (int mto : {1, 2}) {
-            hipError_t e = hipFuncSetAttribute(couple_bwd_ptr(ht, mto), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)lds);
-            if (e != hipSuccess) return e;
-        }
+    for (bool wt : {false, true})
+        for (int ht : {1, 2, 4, 8, 16})
+            for (int mto : {1, 2}) {
+                hipError_t e = hipFuncSetAttribute(couple_bwd_ptr(ht, mto, wt),
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                if (e != hipSuccess) return e;
+            }
     return hipSuccess;
 }
 
@@ -1507,17 +1542,18 @@ int ldw_staging_samples(const LdwArgs& a) { return ldw_samples(a); }
 bool sweep_supported(int ht, int mto) { return sweep_ptr(ht, mto) != nullptr; }
 
 hipError_t set_sweep_lds_limit(size_t lds) {
-    for (int ht : {0, 8, 16})
-        for (int mto : {1, 2}) {
-            hipError_t e = hipFuncSetAttribute(sweep_ptr(ht, mto), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)lds);
-            if (e != hipSuccess) return e;
-        }
+    for (bool wt : {false, true})
+        for (int ht : {0, 8, 16})
+            for (int mto : {1, 2}) {
+                hipError_t e = hipFuncSetAttribute(sweep_ptr(ht, mto, wt), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                   (int)lds);
+                if (e != hipSuccess) return e;
+            }
     return hipSuccess;
 }
 
 hipError_t launch_sweep(int ht, int mto, const SweepJob& j, unsigned grid, size_t lds, hipStream_t st) {
-    void* k = sweep_ptr(j.has_front ? ht : 0, mto);
+    void* k = sweep_ptr(j.has_front ? ht : 0, mto, j.has_front && j.front.wj != nullptr);
     if (!k) return hipErrorInvalidValue;
     void* args[] = {const_cast<SweepJob*>(&j)};
     return hipLaunchKernel(k, dim3(grid), dim3(kBlockThreads), args, lds, st);

@@ -75,6 +75,7 @@ struct TrainArgs {
     int d, n, n_af, kind, phase;
     float inv_n;             // 1 / (global batch size)
     GNet net;
+    const float* wj;         // weighted instances: [sample] w_s / W (j̄ per sample), else nullptr
 };
 
 size_t train_net_lds(int ht, const GNet& g);
@@ -86,6 +87,21 @@ hipError_t train_net_occupancy(int ht, int nh, int am, size_t lds, int* blocks, 
 hipError_t launch_scale(float* dst, const float* src, float s, int64_t count, hipStream_t st);
 hipError_t launch_norm_adjoint(float* zbar, const float* xmin, const float* xmax, float alpha, float beta, int d,
                                int64_t batch, hipStream_t st);
+
+// ---- sample weights (df_train_gradient_w, df_flow_logpdf_wsum) ----
+// The fp64 sums run in a fixed order over spans of kWsumSpan elements, one workgroup each
+// (df_train.hip); `part` holds one double per span (wsum_parts(batch)).
+constexpr int kWsumThreads = 256;
+constexpr int64_t kWsumSpan = 16 * kWsumThreads;
+inline int64_t wsum_parts(int64_t batch) { return (batch + kWsumSpan - 1) / kWsumSpan; }
+// wj[i] = w[i] · (1.f / (float)W), W = w_total if > 0 else Σ w; wsums[1] = W (wsums may be nullptr)
+hipError_t launch_weight_norm(const float* w, int64_t batch, double w_total, double* part, float* wj, double* wsums,
+                              hipStream_t st);
+// *out = Σ w_i · lp_i
+hipError_t launch_weighted_lp_sum(const float* w, const float* lp, int64_t batch, double* part, double* out,
+                                  hipStream_t st);
+// z̄[i][:] = z[i][:] · wj[i] ([sample][d])
+hipError_t launch_scale_rows(float* dst, const float* src, const float* wj, int d, int64_t batch, hipStream_t st);
 hipError_t launch_reduce_grads(const float* partial, int n_parts, int64_t p_total, float* grad, hipStream_t st);
 // Adam update with βᵗ read from bt[0..1] on the device, then βᵗ .*= β (one more launch).
 hipError_t launch_adam(float* x, const float* g, float* m, float* v, int64_t count, float eta, float b1, float b2,
@@ -120,6 +136,13 @@ hipError_t launch_opt_chain(float* x, const float* g, float* m, float* v, float*
 hipError_t launch_batch_gather(float* x_out, float* th_out, const float* x_set, const float* th_set, int d, int n,
                                int64_t n_samples, const int32_t* order, int64_t first, const int64_t* cursor,
                                int64_t batchsize, int64_t count, hipStream_t st);
+// ... and w_out[j] = w_set[row j] in the same launch (the weighted instance of the kernel)
+hipError_t launch_batch_gather_w(float* x_out, float* th_out, float* w_out, const float* x_set, const float* th_set,
+                                 const float* w_set, int d, int n, int64_t n_samples, const int32_t* order,
+                                 int64_t first, const int64_t* cursor, int64_t batchsize, int64_t count,
+                                 hipStream_t st);
+// step_ws[2·*cursor .. +1] = ws[0..1] (step_ws may be nullptr), then *cursor += 1: one thread
+hipError_t launch_cursor_advance_w(int64_t* cursor, const double* ws, double* step_ws, hipStream_t st);
 // *bad (device int) = how many of order[0, n_samples) lie outside [0, n_samples)
 hipError_t launch_order_range(const int32_t* order, int64_t n_samples, int* bad, hipStream_t st);
 // step_lp[*cursor] = *lp (step_lp may be nullptr), then *cursor += 1: one thread

@@ -13,25 +13,26 @@ namespace {
 #endif
 // naf: the transformed-dim count; the SPLIT instances for 2 and 3 (d = 5 chains) have it
 // at compile time (DF_TRAIN_NAF)
-void* train_ptr(int ht, int nh, int am, bool split = false, int naf = 0) {
+template <bool WT>
+void* train_ptr_w(int ht, int nh, int am, bool split, int naf) {
     if (split) {
         if (nh != 1 || am != trn::AM_RELU) return nullptr;
         const int nf = DF_TRAIN_NAF ? naf : 0;
-        if (ht == 2) return nf == 2 ? train_kernel_ptr<2, 1, trn::AM_RELU, true, 2>()
-                            : nf == 3 ? train_kernel_ptr<2, 1, trn::AM_RELU, true, 3>()
-                                      : train_kernel_ptr<2, 1, trn::AM_RELU, true>();
-        if (ht == 4) return nf == 2 ? train_kernel_ptr<4, 1, trn::AM_RELU, true, 2>()
-                            : nf == 3 ? train_kernel_ptr<4, 1, trn::AM_RELU, true, 3>()
-                                      : train_kernel_ptr<4, 1, trn::AM_RELU, true>();
+        if (ht == 2) return nf == 2 ? train_kernel_ptr<2, 1, trn::AM_RELU, true, 2, WT>()
+                            : nf == 3 ? train_kernel_ptr<2, 1, trn::AM_RELU, true, 3, WT>()
+                                      : train_kernel_ptr<2, 1, trn::AM_RELU, true, 0, WT>();
+        if (ht == 4) return nf == 2 ? train_kernel_ptr<4, 1, trn::AM_RELU, true, 2, WT>()
+                            : nf == 3 ? train_kernel_ptr<4, 1, trn::AM_RELU, true, 3, WT>()
+                                      : train_kernel_ptr<4, 1, trn::AM_RELU, true, 0, WT>();
         return nullptr;
     }
 #define DF_T(H)                                                                                           \
-    (nh ? (am == trn::AM_RELU ? train_kernel_ptr<H, 1, trn::AM_RELU>()                                   \
-                              : (am == trn::AM_PRE ? train_kernel_ptr<H, 1, trn::AM_PRE>()                \
-                                                   : train_kernel_ptr<H, 1, trn::AM_Y>()))                \
-        : (am == trn::AM_RELU ? train_kernel_ptr<H, 0, trn::AM_RELU>()                                   \
-                              : (am == trn::AM_PRE ? train_kernel_ptr<H, 0, trn::AM_PRE>()                \
-                                                   : train_kernel_ptr<H, 0, trn::AM_Y>())))
+    (nh ? (am == trn::AM_RELU ? train_kernel_ptr<H, 1, trn::AM_RELU, false, 0, WT>()                     \
+                              : (am == trn::AM_PRE ? train_kernel_ptr<H, 1, trn::AM_PRE, false, 0, WT>()  \
+                                                   : train_kernel_ptr<H, 1, trn::AM_Y, false, 0, WT>()))  \
+        : (am == trn::AM_RELU ? train_kernel_ptr<H, 0, trn::AM_RELU, false, 0, WT>()                     \
+                              : (am == trn::AM_PRE ? train_kernel_ptr<H, 0, trn::AM_PRE, false, 0, WT>()  \
+                                                   : train_kernel_ptr<H, 0, trn::AM_Y, false, 0, WT>())))
     switch (ht) {
         case 1: return DF_T(1);
         case 2: return DF_T(2);
@@ -41,10 +42,76 @@ void* train_ptr(int ht, int nh, int am, bool split = false, int naf = 0) {
 #undef DF_T
 }
 
+// wt: the weighted instance (j̄ per sample from TrainArgs::wj)
+void* train_ptr(int ht, int nh, int am, bool split = false, int naf = 0, bool wt = false) {
+    return wt ? train_ptr_w<true>(ht, nh, am, split, naf) : train_ptr_w<false>(ht, nh, am, split, naf);
+}
+
 // z̄ = z / N
 __global__ void scale_kernel(float* dst, const float* src, float s, int64_t count) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < count) dst[i] = src[i] * s;
+}
+
+// The weighted seed: z̄[i][:] = z[i][:] · wj[i]
+__global__ void scale_rows_kernel(float* dst, const float* src, const float* wj, int d, int64_t count) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) dst[i] = src[i] * wj[i / d];
+}
+
+// ---- sample weights (df_train_gradient_w) ----
+// Fixed-order fp64 sums.  A batch is cut into spans of kWsumSpan elements, one workgroup
+// each: thread t adds its span's elements t, t + 256, ... in increasing order, then the
+// workgroup's tree over LDS; the span sums are added the same way by one workgroup.  The
+// order depends on the element count alone.  v(i) is the i-th term.
+template <typename Term>
+__device__ inline double wsum_block(int64_t count, double* red, Term&& v) {
+    double s = 0.0;
+    for (int64_t i = threadIdx.x; i < count; i += kWsumThreads) s += v(i);
+    __syncthreads();  // (red may still be read from the previous sum)
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int k = kWsumThreads / 2; k >= 1; k >>= 1) {
+        if ((int)threadIdx.x < k) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + k];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+// part[b] = Σ over span b of w_i · lp_i (fp64 product of the two floats), or of w_i (lp == nullptr)
+__global__ __launch_bounds__(kWsumThreads) void wsum_partial_kernel(const float* w, const float* lp, int64_t count,
+                                                                    double* part) {
+    __shared__ double red[kWsumThreads];
+    const int64_t b0 = (int64_t)blockIdx.x * kWsumSpan;
+    const int64_t n = count - b0 < kWsumSpan ? count - b0 : kWsumSpan;
+    const double s = lp ? wsum_block(n, red, [&](int64_t i) { return (double)w[b0 + i] * (double)lp[b0 + i]; })
+                        : wsum_block(n, red, [&](int64_t i) { return (double)w[b0 + i]; });
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(kWsumThreads) void wsum_final_kernel(const double* part, int64_t n_parts, double* out) {
+    __shared__ double red[kWsumThreads];
+    const double s = wsum_block(n_parts, red, [&](int64_t i) { return part[i]; });
+    if (threadIdx.x == 0) *out = s;
+}
+
+// wj = w · inv_W over span blockIdx.x, inv_W = 1.f / (float)W.  W is w_total when that is > 0,
+// else Σ w: the sum of the n_parts span sums in part (every workgroup adds them in the same
+// order), or with one span the sum of w itself.  wsums[1] = W (wsums may be nullptr).  Only
+// w_total comes from the host: a replayed graph sums the weights it finds.
+__global__ __launch_bounds__(kWsumThreads) void weight_norm_kernel(const float* w, int64_t count, double w_total,
+                                                                   const double* part, int64_t n_parts, float* wj,
+                                                                   double* wsums) {
+    __shared__ double red[kWsumThreads];
+    double W = w_total;
+    if (!(w_total > 0.0))
+        W = n_parts > 1 ? wsum_block(n_parts, red, [&](int64_t i) { return part[i]; })
+                        : wsum_block(count, red, [&](int64_t i) { return (double)w[i]; });
+    const float inv_w = 1.f / (float)W;
+    const int64_t b0 = (int64_t)blockIdx.x * kWsumSpan;
+    const int64_t n = count - b0 < kWsumSpan ? count - b0 : kWsumSpan;
+    for (int64_t i = threadIdx.x; i < n; i += kWsumThreads) wj[b0 + i] = w[b0 + i] * inv_w;
+    if (blockIdx.x == 0 && threadIdx.x == 0 && wsums) wsums[1] = W;
 }
 
 // NormalizationLayer inverse z = (β(x - x_min) + α(x_max - x)) / x_diff
@@ -275,18 +342,20 @@ size_t train_net_lds(int ht, const GNet& g) {
 }
 
 hipError_t set_train_lds_limit(size_t lds) {
-    for (int ht : {1, 2, 4})
-        for (int nh = 0; nh < 2; ++nh)
-            for (int am = 0; am < 3; ++am) {
-                hipError_t e = hipFuncSetAttribute(train_ptr(ht, nh, am),
+    for (bool wt : {false, true}) {
+        for (int ht : {1, 2, 4})
+            for (int nh = 0; nh < 2; ++nh)
+                for (int am = 0; am < 3; ++am) {
+                    hipError_t e = hipFuncSetAttribute(train_ptr(ht, nh, am, false, 0, wt),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                    if (e != hipSuccess) return e;
+                }
+        for (int ht : {2, 4}) {
+            for (int naf : {0, 2, 3}) {
+                hipError_t e = hipFuncSetAttribute(train_ptr(ht, 1, trn::AM_RELU, true, naf, wt),
                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
                 if (e != hipSuccess) return e;
             }
-    for (int ht : {2, 4}) {
-        for (int naf : {0, 2, 3}) {
-            hipError_t e = hipFuncSetAttribute(train_ptr(ht, 1, trn::AM_RELU, true, naf),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
         }
     }
     return hipSuccess;
@@ -296,7 +365,7 @@ hipError_t launch_train_net(int ht, int nh, int am, const TrainArgs& a, unsigned
                             hipStream_t st) {
     // out_valu<NO = NAF> needs n_out = n_af, the 4x4x1 x̄ at most 4 conditioner inputs
     const int naf = (a.net.split && a.net.su.n_out == a.n_af && a.net.n_in <= 4) ? a.n_af : 0;
-    void* k = train_ptr(ht, nh, am, a.net.split != 0, naf);
+    void* k = train_ptr(ht, nh, am, a.net.split != 0, naf, a.wj != nullptr);
     if (!k) return hipErrorInvalidValue;
     void* args[] = {const_cast<TrainArgs*>(&a)};
     return hipLaunchKernel(k, dim3(grid), dim3(train_threads(a.net.split != 0)), args, lds, st);
@@ -311,6 +380,38 @@ hipError_t train_net_occupancy(int ht, int nh, int am, size_t lds, int* blocks, 
 hipError_t launch_scale(float* dst, const float* src, float s, int64_t count, hipStream_t st) {
     if (count <= 0) return hipSuccess;
     hipLaunchKernelGGL(scale_kernel, dim3(blocks_for(count, 256)), dim3(256), 0, st, dst, src, s, count);
+    return hipGetLastError();
+}
+
+hipError_t launch_scale_rows(float* dst, const float* src, const float* wj, int d, int64_t batch, hipStream_t st) {
+    const int64_t count = batch * d;
+    if (count <= 0) return hipSuccess;
+    hipLaunchKernelGGL(scale_rows_kernel, dim3(blocks_for(count, 256)), dim3(256), 0, st, dst, src, wj, d, count);
+    return hipGetLastError();
+}
+
+hipError_t launch_weight_norm(const float* w, int64_t batch, double w_total, double* part, float* wj, double* wsums,
+                              hipStream_t st) {
+    const int64_t nb = wsum_parts(batch);
+    if (nb <= 0) return hipSuccess;
+    const bool own = !(w_total > 0.0);
+    if (own && nb > 1)
+        hipLaunchKernelGGL(wsum_partial_kernel, dim3((unsigned)nb), dim3(kWsumThreads), 0, st, w,
+                           static_cast<const float*>(nullptr), batch, part);
+    hipLaunchKernelGGL(weight_norm_kernel, dim3((unsigned)nb), dim3(kWsumThreads), 0, st, w, batch, w_total,
+                       static_cast<const double*>(part), nb, wj, wsums);
+    return hipGetLastError();
+}
+
+hipError_t launch_weighted_lp_sum(const float* w, const float* lp, int64_t batch, double* part, double* out,
+                                  hipStream_t st) {
+    const int64_t nb = wsum_parts(batch);
+    if (nb <= 0) return hipMemsetAsync(out, 0, sizeof(double), st);
+    hipLaunchKernelGGL(wsum_partial_kernel, dim3((unsigned)nb), dim3(kWsumThreads), 0, st, w, lp, batch,
+                       nb == 1 ? out : part);
+    if (nb > 1)
+        hipLaunchKernelGGL(wsum_final_kernel, dim3(1), dim3(kWsumThreads), 0, st, static_cast<const double*>(part), nb,
+                           out);
     return hipGetLastError();
 }
 

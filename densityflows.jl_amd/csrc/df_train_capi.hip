@@ -31,6 +31,7 @@ void free_all(df_train* t) {
     for (TrainGraph& g : t->graphs) drop(g.g);
     t->graphs.clear();
     for (StepGraph& g : t->eg) drop(g);
+    for (StepGraph& g : t->egw) drop(g);
     if (t->cap_stream) (void)hipStreamDestroy(t->cap_stream);
     t->cap_stream = nullptr;
 }
@@ -119,6 +120,111 @@ int setup_chain(df_train* t) {
     return DF_OK;
 }
 
+// The weighted gradient's buffers, sized with the batch buffers (allocated at the first
+// weighted call, so an unweighted trainer's allocations keep their sequence): wj and the
+// per-sample logpdf (float [cap] each) and the span sums of the fp64 reductions.
+int ensure_weight_capacity(df_train* t) {
+    if (t->wcap >= t->cap) return DF_OK;
+    t->cap_gen++;  // captured weighted steps name the old buffers
+    t->wcap = 0;
+    if (t->d_wj.alloc(sizeof(float) * t->cap) != hipSuccess || t->d_wlp.alloc(sizeof(float) * t->cap) != hipSuccess ||
+        t->d_wpart.alloc(sizeof(double) * std::max<int64_t>(wsum_parts(t->cap), 1)) != hipSuccess)
+        return set_err(DF_ERR_NOMEM, "hipMalloc failed (sample weights)");
+    t->wcap = t->cap;
+    return DF_OK;
+}
+
+// The gradient of one mini-batch.  w == nullptr: -mean(logpdf) over n_total, Σ logpdf to *sums
+// (or the trainer's own double).  w: the weighted loss (df_train_gradient_w), {Σ w·lp, W} to
+// sums[0..1]; the sweep's two seeds are then per sample (wj = w / W), from the trainer's
+// weight buffers.
+int gradient(df_train* t, const float* x, const float* theta_raw, const float* w, int64_t batch, int64_t n_total,
+             double w_total, double* sums, void* stream) {
+    df_chain* c = t->c;
+    const Plan& P = c->plan;
+    DeviceGuard gd(c->device);
+    if (!gd.ok) return set_err(DF_ERR_HIP, "hipSetDevice failed");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    double* lp = sums ? sums : t->d_lpsum.as<double>();  // where this gradient writes Σ logpdf
+    t->last_lp = lp;
+    t->last_n = n_total;
+    t->last_ws = w ? lp : nullptr;
+    if (batch == 0) {
+        hipError_t e = hipMemsetAsync(t->d_grad.get(), 0, sizeof(float) * t->tp.n_params, st);
+        if (e == hipSuccess) e = hipMemsetAsync(lp, 0, sizeof(double), st);
+        return e == hipSuccess ? DF_OK : hip_err(e, "hipMemsetAsync");
+    }
+    if (!x) return set_err(DF_ERR_INVALID, "null input array");
+    if (P.n > 0 && !theta_raw)
+        return set_err(DF_ERR_SHAPE, "dimensions θ must match (n, dims...) with n number of trained parameters");
+    const int tf = theta_flow(t);
+    if (tf < 0) return set_err(DF_ERR_INVALID, "θ bounds not set (df_chain_set_theta_bounds) for DF_THETA_RAW");
+    const bool flow = tf == 1;
+    int rc = ensure_capacity(t, batch);
+    if (rc == DF_OK && w) rc = ensure_weight_capacity(t);
+    if (rc != DF_OK) return rc;
+    const BatchBufs& bb = t->bb;
+    float *snap = bb.d_snap.as<float>(), *zbar = bb.d_zbar.as<float>();
+    float *partial = t->d_partial.as<float>(), *grad = t->d_grad.as<float>();
+    float* wj = w ? t->d_wj.as<float>() : nullptr;
+
+    // 1. inverse pass keeping every layer's output (U[li] = snap[li], U[0] = z); weighted:
+    //    logpdf per sample instead of its sum
+    const bool fm = h0free(t);  // H0-free sweep (features + H1 kept)
+    rc = run(c, MODE_LOGPDF, flow, x, theta_raw, nullptr, nullptr, w ? t->d_wlp.as<float>() : nullptr,
+             w ? nullptr : lp, batch,
+             stream, snap, t->hsave_on ? bb.d_hsave.as<float>() : nullptr, t->tp.lwidth, fm ? 1 : t->tp.lmax_h,
+             fm ? bb.d_fsave.as<float>() : nullptr);
+    if (rc != DF_OK) return rc;
+    // 2. z̄ = z / N, or z̄_i = z_i · wj_i after wj = w / W and the two sums
+    const float inv_n = w ? 0.f : 1.f / (float)n_total;
+    hipError_t e;
+    if (w) {
+        double* part = t->d_wpart.as<double>();
+        e = launch_weight_norm(w, batch, w_total, part, wj, lp, st);
+        if (e == hipSuccess) e = launch_weighted_lp_sum(w, t->d_wlp.as<const float>(), batch, part, lp, st);
+        if (e != hipSuccess) return hip_err(e, "weight kernel launch");
+        e = launch_scale_rows(zbar, snap, wj, P.d, batch, st);
+    } else {
+        e = launch_scale(zbar, snap, inv_n, batch * P.d, st);
+    }
+    if (e != hipSuccess) return hip_err(e, "scale kernel launch");
+    // 3. reverse sweep, chain order
+    if (t->tp.layerwise) {
+        rc = lsweep(t, x, theta_raw, batch, inv_n, wj, flow, st);
+        if (rc != DF_OK) return rc;
+        e = launch_reduce_grads(partial, t->lgrid, t->tp.n_params, grad, st);
+        return e == hipSuccess ? DF_OK : hip_err(e, "gradient reduction launch");
+    }
+    const int64_t ntiles = (batch + 15) / 16;
+    const int grid = (int)std::min<int64_t>(t->grid, (ntiles + kTrainWaves - 1) / kTrainWaves);
+    for (const SweepOp& op : t->tp.ops) {
+        if (op.net < 0) {
+            e = norm_adjoint(t, op.layer, zbar, batch, st);
+            if (e != hipSuccess) return hip_err(e, "norm adjoint launch");
+            continue;
+        }
+        TrainArgs a{};
+        fill_layer_args(a, t, op.layer, op.phase, x, theta_raw, flow, batch);
+        a.zbar = zbar;
+        a.ebuf = bb.d_ebuf.as<float>();
+        a.partial = partial;
+        a.blob = c->d_blob.as<const uint8_t>();
+        a.tblob = t->d_tblob.as<const uint8_t>();
+        a.sblob = c->d_sblob.as<const uint8_t>();
+        a.tsblob = t->d_tsblob.as<const uint8_t>();
+        a.p_total = t->tp.n_params;
+        a.inv_n = inv_n;
+        a.wj = wj;
+        a.net = t->tp.nets[op.net];
+        e = launch_train_net(P.ht, t->tp.net_nh[op.net], t->tp.amode, a, (unsigned)grid, t->lds_max, st);
+        if (e != hipSuccess) return hip_err(e, "train kernel launch");
+    }
+    // 4. fixed-order reduction of the workgroup partials
+    e = launch_reduce_grads(partial, grid, t->tp.n_params, grad, st);
+    return e == hipSuccess ? DF_OK : hip_err(e, "gradient reduction launch");
+}
+
 // One step of an epoch on `st`: the mini-batch at the device cursor into the staging
 // buffers, df_train_step on it (Σ logpdf into the trainer's own double), then the cursor
 // moves on and leaves the step's Σ logpdf in step_lp.  Under df_train_set_debug a refused
@@ -136,6 +242,25 @@ int epoch_step(df_train* t, int64_t count, hipStream_t st) {
     if (rc == DF_OK) rc = df_train_apply(t, st);
     if (rc != DF_OK) return rc;
     e = launch_cursor_advance(cursor, t->d_lpsum.as<const double>(), const_cast<double*>(k.step_lp), st);
+    return e == hipSuccess ? DF_OK : hip_err(e, "cursor advance launch");
+}
+
+// The weighted step of an epoch (df_train_epoch_w): the weights gathered with x and θ,
+// df_train_step_w on them, both sums to step_wsums.
+int epoch_step_w(df_train* t, int64_t count, hipStream_t st) {
+    const Plan& P = t->c->plan;
+    const EpochKey& k = t->ekeyw;
+    int64_t* cursor = t->d_cursor.as<int64_t>();
+    float* ex = t->d_ex.as<float>();
+    float* eth = P.n > 0 ? t->d_eth.as<float>() : nullptr;
+    float* ew = t->d_ew.as<float>();
+    hipError_t e = launch_batch_gather_w(ex, eth, ew, k.x_set, k.theta_set, k.w_set, P.d, P.n, k.n_samples, k.order,
+                                         0, cursor, k.batchsize, count, st);
+    if (e != hipSuccess) return hip_err(e, "batch gather launch");
+    int rc = df_train_gradient_w(t, ex, eth, ew, count, 0.0, nullptr, st);
+    if (rc == DF_OK) rc = df_train_apply(t, st);
+    if (rc != DF_OK) return rc;
+    e = launch_cursor_advance_w(cursor, t->d_wsums.as<const double>(), const_cast<double*>(k.step_lp), st);
     return e == hipSuccess ? DF_OK : hip_err(e, "cursor advance launch");
 }
 
@@ -192,6 +317,40 @@ int run_captured(df_train* t, StepGraph& g, hipStream_t st, const char* what, Bo
     }
     const hipError_t e = hipGraphLaunch(g.exec, st);
     return e == hipSuccess ? DF_OK : hip_err(e, where("hipGraphLaunch").c_str());
+}
+
+// df_train_step_graph and df_train_step_graph_w (w != nullptr): the step behind one key of
+// the trainer's graph cache.
+int step_graph(df_train* t, const float* x, const float* theta_raw, const float* w, int64_t batch, int64_t n_total,
+               double w_total, double* sums, void* stream) {
+    DeviceGuard gd(t->c->device);
+    if (!gd.ok) return set_err(DF_ERR_HIP, "hipSetDevice failed");
+    // gradient + update + repack on a stream
+    auto step = [&](hipStream_t s) {
+        const int rc = w ? df_train_gradient_w(t, x, theta_raw, w, batch, w_total, sums, s)
+                         : df_train_gradient(t, x, theta_raw, batch, n_total, sums, s);
+        return rc != DF_OK ? rc : df_train_apply(t, s);
+    };
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (t->debug) return step(st);  // the loss check synchronises: no capture while it is on
+    TrainGraph* g = nullptr;
+    for (TrainGraph& e : t->graphs)
+        if (e.x == x && e.theta == theta_raw && e.lp == sums && e.batch == batch && e.n_total == n_total && e.w == w &&
+            e.w_total == w_total)
+            g = &e;
+    if (!g) {
+        if (t->graphs.size() >= 4) {  // keep the 4 most recently used keys
+            auto lru = t->graphs.begin();
+            for (auto it = t->graphs.begin(); it != t->graphs.end(); ++it)
+                if (it->last_use < lru->last_use) lru = it;
+            drop(lru->g);
+            t->graphs.erase(lru);
+        }
+        t->graphs.push_back({x, theta_raw, sums, batch, n_total, {}, 0, w, w_total});
+        g = &t->graphs.back();
+    }
+    g->last_use = ++t->use_clock;
+    return run_captured(t, g->g, st, "train step", step);
 }
 
 }  // namespace
@@ -353,74 +512,31 @@ int df_train_gradient(df_train* t, const float* x, const float* theta_raw, int64
     if (!t) return set_err(DF_ERR_INVALID, "null trainer");
     if (batch < 0) return set_err(DF_ERR_SHAPE, "negative batch size");
     if (n_total < batch || n_total < 1) return set_err(DF_ERR_INVALID, "n_total must be >= batch and >= 1");
-    df_chain* c = t->c;
-    const Plan& P = c->plan;
-    DeviceGuard gd(c->device);
+    return gradient(t, x, theta_raw, nullptr, batch, n_total, 0.0, logpdf_sum, stream);
+}
+
+int df_train_gradient_w(df_train* t, const float* x, const float* theta_raw, const float* w, int64_t batch,
+                        double w_total, double* wsums, void* stream) {
+    if (!t) return set_err(DF_ERR_INVALID, "null trainer");
+    if (batch < 0) return set_err(DF_ERR_SHAPE, "negative batch size");
+    if (!(w_total >= 0.0)) return set_err(DF_ERR_INVALID, "w_total must be 0 (this batch's own sum) or > 0");
+    if (batch > 0 && !w) return set_err(DF_ERR_INVALID, "null weight array");
+    DeviceGuard gd(t->c->device);
     if (!gd.ok) return set_err(DF_ERR_HIP, "hipSetDevice failed");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    double* lp = logpdf_sum ? logpdf_sum : t->d_lpsum.as<double>();  // where this gradient writes Σ logpdf
-    t->last_lp = lp;
-    t->last_n = n_total;
+    if (!wsums) {
+        if (!t->d_wsums.get() && t->d_wsums.alloc(2 * sizeof(double)) != hipSuccess)
+            return set_err(DF_ERR_NOMEM, "hipMalloc failed (weighted sums)");
+        wsums = t->d_wsums.as<double>();
+    }
     if (batch == 0) {
+        hipStream_t st = static_cast<hipStream_t>(stream);
         hipError_t e = hipMemsetAsync(t->d_grad.get(), 0, sizeof(float) * t->tp.n_params, st);
-        if (e == hipSuccess) e = hipMemsetAsync(lp, 0, sizeof(double), st);
+        if (e == hipSuccess) e = hipMemsetAsync(wsums, 0, 2 * sizeof(double), st);
+        t->last_lp = wsums;
+        t->last_ws = wsums;
         return e == hipSuccess ? DF_OK : hip_err(e, "hipMemsetAsync");
     }
-    if (!x) return set_err(DF_ERR_INVALID, "null input array");
-    if (P.n > 0 && !theta_raw)
-        return set_err(DF_ERR_SHAPE, "dimensions θ must match (n, dims...) with n number of trained parameters");
-    const int tf = theta_flow(t);
-    if (tf < 0) return set_err(DF_ERR_INVALID, "θ bounds not set (df_chain_set_theta_bounds) for DF_THETA_RAW");
-    const bool flow = tf == 1;
-    int rc = ensure_capacity(t, batch);
-    if (rc != DF_OK) return rc;
-    const BatchBufs& bb = t->bb;
-    float *snap = bb.d_snap.as<float>(), *zbar = bb.d_zbar.as<float>();
-    float *partial = t->d_partial.as<float>(), *grad = t->d_grad.as<float>();
-
-    // 1. inverse pass keeping every layer's output (U[li] = snap[li], U[0] = z)
-    const bool fm = h0free(t);  // H0-free sweep (features + H1 kept)
-    rc = run(c, MODE_LOGPDF, flow, x, theta_raw, nullptr, nullptr, nullptr, lp, batch,
-             stream, snap, t->hsave_on ? bb.d_hsave.as<float>() : nullptr, t->tp.lwidth, fm ? 1 : t->tp.lmax_h,
-             fm ? bb.d_fsave.as<float>() : nullptr);
-    if (rc != DF_OK) return rc;
-    // 2. z̄ = z / N
-    const float inv_n = 1.f / (float)n_total;
-    hipError_t e = launch_scale(zbar, snap, inv_n, batch * P.d, st);
-    if (e != hipSuccess) return hip_err(e, "scale kernel launch");
-    // 3. reverse sweep, chain order
-    if (t->tp.layerwise) {
-        rc = lsweep(t, x, theta_raw, batch, inv_n, flow, st);
-        if (rc != DF_OK) return rc;
-        e = launch_reduce_grads(partial, t->lgrid, t->tp.n_params, grad, st);
-        return e == hipSuccess ? DF_OK : hip_err(e, "gradient reduction launch");
-    }
-    const int64_t ntiles = (batch + 15) / 16;
-    const int grid = (int)std::min<int64_t>(t->grid, (ntiles + kTrainWaves - 1) / kTrainWaves);
-    for (const SweepOp& op : t->tp.ops) {
-        if (op.net < 0) {
-            e = norm_adjoint(t, op.layer, zbar, batch, st);
-            if (e != hipSuccess) return hip_err(e, "norm adjoint launch");
-            continue;
-        }
-        TrainArgs a{};
-        fill_layer_args(a, t, op.layer, op.phase, x, theta_raw, flow, batch);
-        a.zbar = zbar;
-        a.ebuf = bb.d_ebuf.as<float>();
-        a.partial = partial;
-        a.blob = c->d_blob.as<const uint8_t>();
-        a.tblob = t->d_tblob.as<const uint8_t>();
-        a.sblob = c->d_sblob.as<const uint8_t>();
-        a.tsblob = t->d_tsblob.as<const uint8_t>();
-        a.p_total = t->tp.n_params;
-        a.inv_n = inv_n;
-        a.net = t->tp.nets[op.net];
-        e = launch_train_net(P.ht, t->tp.net_nh[op.net], t->tp.amode, a, (unsigned)grid, t->lds_max, st);
-        if (e != hipSuccess) return hip_err(e, "train kernel launch");
-    }
-    // 4. fixed-order reduction of the workgroup partials
-    e = launch_reduce_grads(partial, grid, t->tp.n_params, grad, st);
-    return e == hipSuccess ? DF_OK : hip_err(e, "gradient reduction launch");
+    return gradient(t, x, theta_raw, w, batch, batch, w_total, wsums, stream);
 }
 
 int df_train_logpdf_grad(df_train* t, const float* x, const float* theta, float* logpdf_out, float* grad_x,
@@ -535,11 +651,14 @@ int df_train_apply(df_train* t, void* stream) {
     DeviceGuard gd(t->c->device);
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (t->debug && t->last_lp) {  // train!(...; debug=true), src/Flows.jl:404-409
-        double s = 0.0;
-        hipError_t e = hipMemcpyAsync(&s, t->last_lp, sizeof(double), hipMemcpyDeviceToHost, st);
+        // (a weighted gradient left {Σ w·lp, W}: its loss is over W, and W <= 0 is refused too)
+        double s[2] = {0.0, 0.0};
+        const bool wt = t->last_ws != nullptr;
+        hipError_t e = hipMemcpyAsync(s, t->last_lp, (wt ? 2 : 1) * sizeof(double), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e != hipSuccess) return hip_err(e, "debug loss read-back");
-        const double l = -s / (double)(t->last_n > 0 ? t->last_n : 1);
+        const double l = wt ? (s[1] > 0.0 ? -s[0] / s[1] : std::nan(""))
+                            : -s[0] / (double)(t->last_n > 0 ? t->last_n : 1);
         if (!std::isfinite(l)) {
             char msg[96];
             std::snprintf(msg, sizeof msg, "non-finite training loss %g: parameters not updated", l);
@@ -576,37 +695,31 @@ int df_train_step(df_train* t, const float* x, const float* theta_raw, int64_t b
     return rc != DF_OK ? rc : df_train_apply(t, stream);
 }
 
+int df_train_step_w(df_train* t, const float* x, const float* theta_raw, const float* w, int64_t batch,
+                    double* wsums, void* stream) {
+    if (!t) return set_err(DF_ERR_INVALID, "null trainer");
+    if (batch == 0) return DF_OK;
+    int rc = df_train_gradient_w(t, x, theta_raw, w, batch, 0.0, wsums, stream);
+    return rc != DF_OK ? rc : df_train_apply(t, stream);
+}
+
 int df_train_step_graph(df_train* t, const float* x, const float* theta_raw, int64_t batch, int64_t n_total,
                         double* logpdf_sum, void* stream) {
     if (!t) return set_err(DF_ERR_INVALID, "null trainer");
     if (batch == 0) return DF_OK;
     if (batch < 0) return set_err(DF_ERR_SHAPE, "negative batch size");
     if (n_total < batch) return set_err(DF_ERR_INVALID, "n_total must be >= batch and >= 1");
-    DeviceGuard gd(t->c->device);
-    if (!gd.ok) return set_err(DF_ERR_HIP, "hipSetDevice failed");
-    // gradient + update + repack on a stream
-    auto step = [&](hipStream_t s) {
-        const int rc = df_train_gradient(t, x, theta_raw, batch, n_total, logpdf_sum, s);
-        return rc != DF_OK ? rc : df_train_apply(t, s);
-    };
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (t->debug) return step(st);  // the loss check synchronises: no capture while it is on
-    TrainGraph* g = nullptr;
-    for (TrainGraph& e : t->graphs)
-        if (e.x == x && e.theta == theta_raw && e.lp == logpdf_sum && e.batch == batch && e.n_total == n_total) g = &e;
-    if (!g) {
-        if (t->graphs.size() >= 4) {  // keep the 4 most recently used keys
-            auto lru = t->graphs.begin();
-            for (auto it = t->graphs.begin(); it != t->graphs.end(); ++it)
-                if (it->last_use < lru->last_use) lru = it;
-            drop(lru->g);
-            t->graphs.erase(lru);
-        }
-        t->graphs.push_back({x, theta_raw, logpdf_sum, batch, n_total, {}, 0});
-        g = &t->graphs.back();
-    }
-    g->last_use = ++t->use_clock;
-    return run_captured(t, g->g, st, "train step", step);
+    return step_graph(t, x, theta_raw, nullptr, batch, n_total, 0.0, logpdf_sum, stream);
+}
+
+int df_train_step_graph_w(df_train* t, const float* x, const float* theta_raw, const float* w, int64_t batch,
+                          double w_total, double* wsums, void* stream) {
+    if (!t) return set_err(DF_ERR_INVALID, "null trainer");
+    if (batch == 0) return DF_OK;
+    if (batch < 0) return set_err(DF_ERR_SHAPE, "negative batch size");
+    if (!(w_total >= 0.0)) return set_err(DF_ERR_INVALID, "w_total must be 0 (this batch's own sum) or > 0");
+    if (!w) return set_err(DF_ERR_INVALID, "null weight array");
+    return step_graph(t, x, theta_raw, w, batch, batch, w_total, wsums, stream);
 }
 
 int df_batch_gather(float* x_out, float* theta_out, const float* x_set, const float* theta_set, int d, int n,
@@ -623,8 +736,11 @@ int df_batch_gather(float* x_out, float* theta_out, const float* x_set, const fl
     return e == hipSuccess ? DF_OK : hip_err(e, "batch gather launch");
 }
 
-int df_train_epoch(df_train* t, const float* x_set, const float* theta_set, int64_t n_samples, const int32_t* order,
-                   int64_t batchsize, double* step_logpdf_sum, int64_t* steps_done, void* stream) {
+// df_train_epoch, and df_train_epoch_w (weighted: w_set is read, the steps are epoch_step_w in
+// the weighted graph slots, step_sums takes two doubles per step).
+static int epoch(df_train* t, const float* x_set, const float* theta_set, const float* w_set, bool weighted,
+                 int64_t n_samples, const int32_t* order, int64_t batchsize, double* step_logpdf_sum,
+                 int64_t* steps_done, void* stream) {
     if (!t) return set_err(DF_ERR_INVALID, "null trainer");
     if (steps_done) *steps_done = 0;
     if (batchsize <= 0) return set_err(DF_ERR_INVALID, "batchsize must be >= 1");
@@ -632,6 +748,7 @@ int df_train_epoch(df_train* t, const float* x_set, const float* theta_set, int6
     if (n_samples == 0) return DF_OK;
     if (n_samples >= (int64_t)1 << 31) return set_err(DF_ERR_SHAPE, "a resident set holds fewer than 2^31 samples");
     if (!x_set) return set_err(DF_ERR_INVALID, "null input array");
+    if (weighted && !w_set) return set_err(DF_ERR_INVALID, "null weight array");
     df_chain* c = t->c;
     const Plan& P = c->plan;
     if (P.n > 0 && !theta_set)
@@ -663,18 +780,29 @@ int df_train_epoch(df_train* t, const float* x_set, const float* theta_set, int6
 
     // staging for one mini-batch; the captured steps name it and everything in the key
     const int64_t full = std::min(batchsize, n_samples);
-    const EpochKey key{x_set, theta_set, order, step_logpdf_sum, n_samples, batchsize};
+    const EpochKey key{x_set, theta_set, order, step_logpdf_sum, n_samples, batchsize, w_set};
+    StepGraph* const eg = weighted ? t->egw : t->eg;
+    int64_t* const eg_count = weighted ? t->egw_count : t->eg_count;
+    EpochKey& ekey = weighted ? t->ekeyw : t->ekey;
     if (full > t->ecap) {
         for (StepGraph& g : t->eg) drop(g);
+        for (StepGraph& g : t->egw) drop(g);
         t->ecap = 0;
         if (t->d_ex.alloc(sizeof(float) * (size_t)full * P.d) != hipSuccess ||
             (P.n > 0 && t->d_eth.alloc(sizeof(float) * (size_t)full * P.n) != hipSuccess))
             return set_err(DF_ERR_NOMEM, "hipMalloc failed (mini-batch staging)");
         t->ecap = full;
     }
-    if (!(key == t->ekey))
-        for (StepGraph& g : t->eg) drop(g);
-    t->ekey = key;
+    if (weighted && full > t->ewcap) {  // (the weights' staging comes with the first weighted epoch)
+        for (StepGraph& g : t->egw) drop(g);
+        t->ewcap = 0;
+        if (t->d_ew.alloc(sizeof(float) * (size_t)t->ecap) != hipSuccess)
+            return set_err(DF_ERR_NOMEM, "hipMalloc failed (mini-batch staging)");
+        t->ewcap = t->ecap;
+    }
+    if (!(key == ekey))
+        for (int k = 0; k < 2; ++k) drop(eg[k]);
+    ekey = key;
 
     hipError_t e = hipMemsetAsync(cursor, 0, sizeof(int64_t), st);
     if (e != hipSuccess) return hip_err(e, "hipMemsetAsync");
@@ -684,10 +812,10 @@ int df_train_epoch(df_train* t, const float* x_set, const float* theta_set, int6
         // as df_train_step_graph runs its step; a slot captured for another count is dropped first.
         // Debug mode: the per-step loss check synchronises, so the steps run eagerly
         const int slot = count == full ? 0 : 1;
-        if (t->eg_count[slot] != count) drop(t->eg[slot]);
-        t->eg_count[slot] = count;
-        auto step = [&](hipStream_t on) { return epoch_step(t, count, on); };
-        const int rc = t->debug ? step(st) : run_captured(t, t->eg[slot], st, "epoch step", step);
+        if (eg_count[slot] != count) drop(eg[slot]);
+        eg_count[slot] = count;
+        auto step = [&](hipStream_t on) { return weighted ? epoch_step_w(t, count, on) : epoch_step(t, count, on); };
+        const int rc = t->debug ? step(st) : run_captured(t, eg[slot], st, "epoch step", step);
         if (rc != DF_OK) {
             if (steps_done) *steps_done = i;
             return rc;
@@ -695,6 +823,72 @@ int df_train_epoch(df_train* t, const float* x_set, const float* theta_set, int6
     }
     if (steps_done) *steps_done = steps;
     return DF_OK;
+}
+
+int df_train_epoch(df_train* t, const float* x_set, const float* theta_set, int64_t n_samples, const int32_t* order,
+                   int64_t batchsize, double* step_logpdf_sum, int64_t* steps_done, void* stream) {
+    return epoch(t, x_set, theta_set, nullptr, false, n_samples, order, batchsize, step_logpdf_sum, steps_done, stream);
+}
+
+int df_train_epoch_w(df_train* t, const float* x_set, const float* theta_set, const float* w_set, int64_t n_samples,
+                     const int32_t* order, int64_t batchsize, double* step_wsums, int64_t* steps_done, void* stream) {
+    return epoch(t, x_set, theta_set, w_set, true, n_samples, order, batchsize, step_wsums, steps_done, stream);
+}
+
+int df_batch_gather_w(float* x_out, float* theta_out, float* w_out, const float* x_set, const float* theta_set,
+                      const float* w_set, int d, int n, int64_t n_samples, const int32_t* order, int64_t first,
+                      int64_t count, void* stream) {
+    if (d < 1 || n < 0) return set_err(DF_ERR_INVALID, "df_batch_gather_w: d >= 1 and n >= 0");
+    if (count < 0 || n_samples < 0) return set_err(DF_ERR_SHAPE, "negative sample count");
+    if (n_samples >= (int64_t)1 << 31) return set_err(DF_ERR_SHAPE, "a resident set holds fewer than 2^31 samples");
+    if (first < 0 || first + count > n_samples)
+        return set_err(DF_ERR_INVALID, "df_batch_gather_w: [first, first + count) must lie inside [0, n_samples)");
+    if (count == 0) return DF_OK;
+    if (!x_out || !x_set || !w_out || !w_set || (n > 0 && (!theta_out || !theta_set)))
+        return set_err(DF_ERR_INVALID, "null array");
+    const hipError_t e = launch_batch_gather_w(x_out, theta_out, w_out, x_set, theta_set, w_set, d, n, n_samples, order,
+                                               first, nullptr, 0, count, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? DF_OK : hip_err(e, "batch gather launch");
+}
+
+static int logpdf_wsum(df_chain* c, bool flow, const float* x, const float* theta, const float* w, int64_t batch,
+                       double* wsums, void* stream) {
+    if (!c) return set_err(DF_ERR_INVALID, "null chain");
+    if (!wsums) return set_err(DF_ERR_INVALID, "null sum output");
+    if (batch < 0) return set_err(DF_ERR_SHAPE, "negative batch size");
+    DeviceGuard gd(c->device);
+    if (!gd.ok) return set_err(DF_ERR_HIP, "hipSetDevice failed");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (batch == 0) {
+        const hipError_t e = hipMemsetAsync(wsums, 0, 2 * sizeof(double), st);
+        return e == hipSuccess ? DF_OK : hip_err(e, "hipMemsetAsync");
+    }
+    if (!w) return set_err(DF_ERR_INVALID, "null weight array");
+    if (batch > c->wlp_cap) {
+        c->wlp_cap = 0;
+        const int64_t cap = std::max<int64_t>(batch, 1024);
+        if (c->d_wlp.alloc(sizeof(float) * cap) != hipSuccess ||
+            c->d_wlp_part.alloc(sizeof(double) * wsum_parts(cap)) != hipSuccess)
+            return set_err(DF_ERR_NOMEM, "hipMalloc failed (weighted logpdf workspace)");
+        c->wlp_cap = cap;
+    }
+    float* lp = c->d_wlp.as<float>();
+    double* part = c->d_wlp_part.as<double>();
+    const int rc = run(c, MODE_LOGPDF, flow, x, theta, nullptr, nullptr, lp, nullptr, batch, stream);
+    if (rc != DF_OK) return rc;
+    hipError_t e = launch_weighted_lp_sum(w, lp, batch, part, wsums, st);
+    if (e == hipSuccess) e = launch_weighted_lp_sum(w, nullptr, batch, part, wsums + 1, st);
+    return e == hipSuccess ? DF_OK : hip_err(e, "weighted sum launch");
+}
+
+int df_flow_logpdf_wsum(df_chain* c, const float* x, const float* theta_raw, const float* w, int64_t batch,
+                        double* wsums, void* stream) {
+    return logpdf_wsum(c, true, x, theta_raw, w, batch, wsums, stream);
+}
+
+int df_chain_logpdf_wsum(df_chain* c, const float* x, const float* theta, const float* w, int64_t batch,
+                         double* wsums, void* stream) {
+    return logpdf_wsum(c, false, x, theta, w, batch, wsums, stream);
 }
 
 int df_train_set_debug(df_train* t, int on) {

@@ -194,7 +194,8 @@ __device__ __forceinline__ f32x4 mfma4x4(float a, float b, f32x4 c) {
 // NAF > 0: the transformed-dim count (= output count) at compile time (SPLIT instances,
 // 2 and 3: the d = 5 chains; the launcher also requires ≤ 4 conditioner inputs);
 // 0: a.n_af at run time.
-template <int HT, int NH, int AM, bool SPLIT = false, int NAF = 0>
+// WT: the weighted loss (df_train_gradient_w): j̄ of sample s is a.wj[s] = w_s / W, not a.inv_n.
+template <int HT, int NH, int AM, bool SPLIT = false, int NAF = 0, bool WT = false>
 __global__ void __launch_bounds__(train_threads(SPLIT), 1) train_net_kernel(TrainArgs a) {
     using namespace trn;
     const int n_af = NAF > 0 ? NAF : a.n_af;
@@ -401,6 +402,12 @@ __global__ void __launch_bounds__(train_threads(SPLIT), 1) train_net_kernel(Trai
         }
 #pragma unroll
         for (int t = 0; t < TT; ++t) load_pull(s[t], valid[t], zbp[t], aux[t]);
+        float jb[TT];  // j̄ of this lane's sample (WT: loaded with the pullback's operands)
+#pragma unroll
+        for (int t = 0; t < TT; ++t) {
+            jb[t] = a.inv_n;
+            if constexpr (WT) jb[t] = (valid[t] && sph) ? a.wj[s[t]] : 0.f;
+        }
         if constexpr (SPLIT) {
             uni::dense_hidden_split<HT, TT, true, true>(fw + N.off_h, A0, A1);
             uni::bias_act<HT, TT, true>(fw, DF_ACT_RELU, A1, false);
@@ -442,7 +449,7 @@ __global__ void __launch_bounds__(train_threads(SPLIT), 1) train_net_kernel(Trai
                     zb[t][k] = zbp[t][k];
                     if (sph) {
                         ee[t][k] = expf(-o[t][k]);
-                        dout[t][k] = -zb[t][k] * aux[t][k] + a.inv_n;  // s̄ = -z̄_af·z_af - j̄
+                        dout[t][k] = -zb[t][k] * aux[t][k] + jb[t];    // s̄ = -z̄_af·z_af - j̄
                     } else {
                         if (rnvp) ee[t][k] = aux[t][k];
                         dout[t][k] = -zb[t][k] * ee[t][k];             // t̄ = -z̄_af·exp(-s)
@@ -792,9 +799,9 @@ __global__ void __launch_bounds__(train_threads(SPLIT), 1) train_net_kernel(Trai
     }
 }
 
-template <int HT, int NH, int AM, bool SPLIT = false, int NAF = 0>
+template <int HT, int NH, int AM, bool SPLIT = false, int NAF = 0, bool WT = false>
 void* train_kernel_ptr() {
-    return reinterpret_cast<void*>(&train_net_kernel<HT, NH, AM, SPLIT, NAF>);
+    return reinterpret_cast<void*>(&train_net_kernel<HT, NH, AM, SPLIT, NAF, WT>);
 }
 
 }  // namespace df

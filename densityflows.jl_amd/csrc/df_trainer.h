@@ -31,6 +31,8 @@ struct TrainGraph {
     int64_t batch = 0, n_total = 0;
     StepGraph g;
     uint64_t last_use = 0;
+    const void* w = nullptr;  // df_train_step_graph_w: the weight buffer and w_total
+    double w_total = 0.0;
 };
 
 // What a captured epoch step names besides the trainer's own buffers.
@@ -40,9 +42,10 @@ struct EpochKey {
     const int32_t* order = nullptr;
     const double* step_lp = nullptr;
     int64_t n_samples = 0, batchsize = 0;
+    const float* w_set = nullptr;  // df_train_epoch_w
     bool operator==(const EpochKey& o) const {
         return x_set == o.x_set && theta_set == o.theta_set && order == o.order && step_lp == o.step_lp &&
-               n_samples == o.n_samples && batchsize == o.batchsize;
+               n_samples == o.n_samples && batchsize == o.batchsize && w_set == o.w_set;
     }
 };
 
@@ -92,6 +95,13 @@ struct df_train {
     int theta_input = DF_THETA_AUTO;  // df_train_set_theta_input
     const double* last_lp = nullptr;  // Σ logpdf written by the last df_train_gradient
     int64_t last_n = 0;               // ... and the n_total it was taken over
+    // a weighted gradient (df_train_gradient_w) wrote {Σ w·lp, W} at last_lp: last_ws == last_lp, else nullptr
+    const double* last_ws = nullptr;
+    // the weighted gradient's buffers (ensure_weight_capacity, at the first weighted call):
+    // wj = w / W and the per-sample logpdf, float [wcap]; the span sums of the fp64
+    // reductions; the trainer's own {Σ w·lp, W}
+    DevBuf d_wj, d_wlp, d_wpart, d_wsums;
+    int64_t wcap = 0;
     int64_t cap = 0;       // batch capacity of bb
     int grid = 0;          // workgroups of a full net launch (resident on the device)
     size_t lds_max = 0;
@@ -119,6 +129,13 @@ struct df_train {
     EpochKey ekey;
     StepGraph eg[2];
     int64_t eg_count[2] = {0, 0};
+    // df_train_epoch_w: the gathered weights (float [ewcap]) and the weighted steps' own key
+    // and graph slots
+    DevBuf d_ew;
+    int64_t ewcap = 0;
+    EpochKey ekeyw;
+    StepGraph egw[2];
+    int64_t egw_count[2] = {0, 0};
 };
 
 // the H0-free sweep is planned and its buffers fit (ensure_capacity)
@@ -174,4 +191,6 @@ inline hipError_t norm_adjoint(const df_train* t, int layer, float* zbar, int64_
 // df_lsweep.hip: the dynamic LDS its kernel families declare (df_train_create_opt), and the
 // reverse sweep of the layer-wise path (chain order, see df_ltrain.h).
 hipError_t lsweep_set_lds_limits();
-int lsweep(df_train* t, const float* x, const float* theta, int64_t batch, float inv_n, bool flow, hipStream_t st);
+// wj: the weighted loss's j̄ per sample (nullptr: inv_n for every sample)
+int lsweep(df_train* t, const float* x, const float* theta, int64_t batch, float inv_n, const float* wj, bool flow,
+           hipStream_t st);

@@ -73,9 +73,14 @@ class DataPartition:
 
 
 class DataArrays:
-    """``DataArrays(x, θ = dflt_θ(x); f_training, f_validation, rng)`` — src/Data.jl:131-170."""
+    """``DataArrays(x, θ = dflt_θ(x); f_training, f_validation, rng)`` — src/Data.jl:131-170.
 
-    def __init__(self, x, theta=None, f_training=0.9, f_validation=0.1, rng=None):
+    ``weights``: one weight per sample (nested-sampling or importance weights, event weights),
+    shape ``x.shape[1:]``, finite and >= 0; ``train_`` then minimises ``-Σ w·logpdf / Σ w``.
+    They are checked here, and each split must keep some weight (``ArgumentError`` naming the
+    offending index)."""
+
+    def __init__(self, x, theta=None, f_training=0.9, f_validation=0.1, rng=None, weights=None):
         x = np.asarray(x, dtype=np.float32)
         if x.ndim < 2:
             raise AssertionError("data must be an array of size (d, i1, ...) at least")
@@ -85,6 +90,21 @@ class DataArrays:
         self.x = x
         self.theta = theta
         self.partition = DataPartition.random(x.shape[1], f_training, f_validation, rng)
+        self.weights = None
+        if weights is not None:
+            from ._lib import ArgumentError
+            from .train import check_weights
+
+            w = np.asarray(weights)
+            if tuple(w.shape) != tuple(x.shape[1:]):
+                raise ArgumentError(f"weights must have shape {tuple(x.shape[1:])}, one per sample; got {tuple(w.shape)}")
+            if w.ndim != 1:
+                raise ArgumentError("weights need x of shape (d, N): one weight per column")
+            self.weights = check_weights(w, x.shape[1])
+            for name, idx in (("training", self.partition.training), ("validation", self.partition.validation)):
+                if idx.size and not np.any(self.weights[idx] > 0):
+                    raise ArgumentError(f"weights: the {name} split holds only zero weights "
+                                        f"(its first sample is index {int(idx[0])})")
 
     def number_dimensions(self) -> int:
         return self.x.shape[0]
@@ -103,6 +123,13 @@ class DataArrays:
 
     def testing_data(self):
         return self._select(self.partition.testing)
+
+    def training_weights(self):
+        """The training split's weights, in ``training_data()``'s sample order (None without weights)."""
+        return None if self.weights is None else np.take(self.weights, self.partition.training)
+
+    def validation_weights(self):
+        return None if self.weights is None else np.take(self.weights, self.partition.validation)
 
     def summarize(self) -> str:
         return (f"Data with size {self.x.shape} and parameters / conditions with size {self.theta.shape}.")

@@ -266,6 +266,13 @@ class HIPChain:
                                                C.c_void_p(sumbuf.data_ptr()), C.c_int64(batch),
                                                _stream(self.device)), "logpdf_sum")
 
+    def run_logpdf_wsum(self, xbuf, thbuf, wbuf, sumbuf, batch: int):
+        """df_flow_logpdf_wsum on flat device buffers: ``{Σ w·logpdf, Σ w}`` into the two
+        float64 of ``sumbuf``."""
+        _lib.check(self.lib.df_flow_logpdf_wsum(self.handle, _ptr(xbuf), _ptr(thbuf), _ptr(wbuf),
+                                                C.c_int64(batch), C.c_void_p(sumbuf.data_ptr()),
+                                                _stream(self.device)), "logpdf_wsum")
+
     def run_logpdf_grid(self, axes_buf, lens, first: int, count: int, lpbuf, chunk: int = 0):
         """df_flow_logpdf_grid: logpdf on points [first, first + count) of the outer product of
         the d + n axis vectors concatenated in ``axes_buf`` (first axis fastest), evaluated

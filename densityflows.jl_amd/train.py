@@ -29,7 +29,7 @@ from .hip import HIPChain, _ptr, _stream, as_julia_device, flatten_elements
 from .layers import NormalizationLayer, RNVPCouplingLayer
 
 __all__ = ["Adam", "Descent", "ClipGrad", "ClipNorm", "WeightDecay", "OptimiserChain", "AdamW", "setup", "adjust_",
-           "TrainState", "HIPTrainer", "train_", "trainables", "load_trainables"]
+           "TrainState", "HIPTrainer", "train_", "trainables", "load_trainables", "weighted_nll", "check_weights"]
 
 
 class Adam:
@@ -237,44 +237,90 @@ class HIPTrainer:
         _lib.check(self.lib.df_train_grad_ptr(self.handle, C.byref(p)))
         return torch.as_tensor(_DeviceArray(p.value or 0, self.num_params), device=self.device)
 
-    def gradient(self, xbuf, thbuf, batch: int, n_total: int, lpsum=None):
+    def gradient(self, xbuf, thbuf, batch: int, n_total: int = None, lpsum=None, w=None, w_total: float = 0.0,
+                 wsums=None):
+        """df_train_gradient, or with ``w`` (a float32 device tensor of ``batch`` sample weights)
+        df_train_gradient_w: the gradient of ``-Σ w·logpdf / W``.  ``w_total``: 0 for ``W = Σ w``
+        of this batch, or the global sum a data-parallel shard divides by; ``wsums``: a float64
+        device tensor of 2 for ``{Σ w·logpdf, W}``, or None."""
+        if w is not None:
+            _check_w_total(w_total)
+            _lib.check(self.lib.df_train_gradient_w(self.handle, _ptr(xbuf), _ptr(thbuf), _ptr(w), C.c_int64(batch),
+                                                    C.c_double(w_total), _ptr(wsums), _stream(self.device)),
+                       "df_train_gradient_w")
+            return
         _lib.check(self.lib.df_train_gradient(self.handle, _ptr(xbuf), _ptr(thbuf), C.c_int64(batch),
-                                              C.c_int64(n_total), _ptr(lpsum), _stream(self.device)),
+                                              C.c_int64(batch if n_total is None else n_total), _ptr(lpsum),
+                                              _stream(self.device)),
                    "df_train_gradient")
 
     def apply(self):
         _lib.check(self.lib.df_train_apply(self.handle, _stream(self.device)), "df_train_apply")
 
-    def step(self, xbuf, thbuf, batch: int, lpsum=None):
+    def step(self, xbuf, thbuf, batch: int, lpsum=None, w=None, wsums=None):
+        """df_train_step; with ``w`` df_train_step_w (``wsums``: see :meth:`gradient`)."""
+        if w is not None:
+            _lib.check(self.lib.df_train_step_w(self.handle, _ptr(xbuf), _ptr(thbuf), _ptr(w), C.c_int64(batch),
+                                                _ptr(wsums), _stream(self.device)), "df_train_step_w")
+            return
         _lib.check(self.lib.df_train_step(self.handle, _ptr(xbuf), _ptr(thbuf), C.c_int64(batch), _ptr(lpsum),
                                           _stream(self.device)), "df_train_step")
 
-    def step_graph(self, xbuf, thbuf, batch: int, n_total: int = None, lpsum=None):
+    def step_graph(self, xbuf, thbuf, batch: int, n_total: int = None, lpsum=None, w=None, w_total: float = 0.0,
+                   wsums=None):
         """gradient + apply replayed as one hipGraph once the same buffers repeat
-        (df_train_step_graph); pass persistent staging buffers."""
+        (df_train_step_graph); pass persistent staging buffers.  With ``w`` the weighted step
+        (df_train_step_graph_w): ``W`` is summed inside the graph, so the weight buffer may be
+        rewritten between calls like ``xbuf``."""
+        if w is not None:
+            _check_w_total(w_total)
+            _lib.check(self.lib.df_train_step_graph_w(self.handle, _ptr(xbuf), _ptr(thbuf), _ptr(w), C.c_int64(batch),
+                                                      C.c_double(w_total), _ptr(wsums), _stream(self.device)),
+                       "df_train_step_graph_w")
+            return
         n_total = batch if n_total is None else n_total
         _lib.check(self.lib.df_train_step_graph(self.handle, _ptr(xbuf), _ptr(thbuf), C.c_int64(batch),
                                                 C.c_int64(n_total), _ptr(lpsum), _stream(self.device)),
                    "df_train_step_graph")
 
-    def gather(self, x_out, theta_out, x_set, theta_set, n_samples: int, order, first: int, count: int):
+    def gather(self, x_out, theta_out, x_set, theta_set, n_samples: int, order, first: int, count: int, w=None):
         """df_batch_gather on flat device buffers: samples ``order[first : first + count]`` of the
         resident set (``x_set`` (n_samples·d,), ``theta_set`` (n_samples·n,), Julia order; ``order``
         an int32 device tensor or None for ``first + j``) into the first ``count`` samples of
-        ``x_out`` / ``theta_out``."""
+        ``x_out`` / ``theta_out``.  ``w``: a pair ``(w_out, w_set)`` of float32 device tensors;
+        the set's weights are then gathered in the same launch (df_batch_gather_w)."""
+        if w is not None:
+            w_out, w_set = w
+            _lib.check(self.lib.df_batch_gather_w(_ptr(x_out), _ptr(theta_out), _ptr(w_out), _ptr(x_set),
+                                                  _ptr(theta_set), _ptr(w_set), C.c_int(self.chain.d),
+                                                  C.c_int(self.chain.n), C.c_int64(n_samples), _ptr(order),
+                                                  C.c_int64(first), C.c_int64(count), _stream(self.device)),
+                       "df_batch_gather_w")
+            return
         _lib.check(self.lib.df_batch_gather(_ptr(x_out), _ptr(theta_out), _ptr(x_set), _ptr(theta_set),
                                             C.c_int(self.chain.d), C.c_int(self.chain.n), C.c_int64(n_samples),
                                             _ptr(order), C.c_int64(first), C.c_int64(count), _stream(self.device)),
                    "df_batch_gather")
 
-    def epoch(self, x_set, theta_set, n_samples: int, order, batchsize: int, step_lp=None) -> int:
+    def epoch(self, x_set, theta_set, n_samples: int, order, batchsize: int, step_lp=None, w=None,
+              step_wsums=None) -> int:
         """df_train_epoch: one epoch of mini-batch steps on a resident set, enqueued without
         waiting for them.  ``order``: an int32 device tensor of ``n_samples`` indices, or None
         for the set's own order; ``step_lp``: a float64 device tensor with one entry per step
         (ceil(n_samples / batchsize)) for every step's Σ logpdf, or None.  Returns the number of
         steps enqueued, also kept in ``steps_done``; when debug mode refuses a step
-        (NonFiniteError), ``steps_done`` is that step's index."""
+        (NonFiniteError), ``steps_done`` is that step's index.  ``w``: the set's weights, a
+        float32 device tensor of ``n_samples`` (df_train_epoch_w: every step is the weighted
+        step on its gathered weights); ``step_wsums`` then takes 2 float64 per step,
+        ``{Σ w·logpdf, W}``."""
         done = C.c_int64(0)
+        if w is not None:
+            rc = self.lib.df_train_epoch_w(self.handle, _ptr(x_set), _ptr(theta_set), _ptr(w), C.c_int64(n_samples),
+                                           _ptr(order), C.c_int64(batchsize), _ptr(step_wsums), C.byref(done),
+                                           _stream(self.device))
+            self.steps_done = int(done.value)
+            _lib.check(rc, "df_train_epoch_w")
+            return self.steps_done
         rc = self.lib.df_train_epoch(self.handle, _ptr(x_set), _ptr(theta_set), C.c_int64(n_samples), _ptr(order),
                                      C.c_int64(batchsize), _ptr(step_lp), C.byref(done), _stream(self.device))
         self.steps_done = int(done.value)
@@ -349,6 +395,52 @@ class HIPTrainer:
                                                 C.c_int64(flat.shape[0])))
 
 
+def _check_w_total(w_total) -> None:
+    if not float(w_total) >= 0.0:  # negative or NaN
+        raise _lib.ArgumentError(f"w_total must be 0 (the batch's own Σ w) or > 0, got {w_total!r}")
+
+
+def check_weights(w, count: int, what: str = "weights") -> np.ndarray:
+    """Host-side check of a weight array before the library is touched (the C calls do not
+    check, that would synchronise): shape ``(count,)``, every entry finite and >= 0, not all
+    zero.  Raises ``ArgumentError`` naming the first offending index; returns float32."""
+    w = np.asarray(w)
+    if w.ndim != 1 or w.shape[0] != int(count):
+        raise _lib.ArgumentError(f"{what} must have shape ({int(count)},), one per sample; got {tuple(w.shape)}")
+    w = w.astype(np.float32, copy=False)
+    bad = np.flatnonzero(~np.isfinite(w))
+    if bad.size:
+        raise _lib.ArgumentError(f"{what}[{int(bad[0])}] = {w[bad[0]]} is not finite")
+    neg = np.flatnonzero(w < 0)
+    if neg.size:
+        raise _lib.ArgumentError(f"{what}[{int(neg[0])}] = {w[neg[0]]} is negative")
+    if count > 0 and not np.any(w > 0):
+        raise _lib.ArgumentError(f"{what}: all {int(count)} weights are zero (index 0 onwards), Σ w must be > 0")
+    return np.ascontiguousarray(w)
+
+
+def weighted_nll(flow, x, theta, w):
+    """``(loss, W)`` with ``loss = -Σ w·logpdf / W`` and ``W = Σ w`` over a set, both sums in
+    fp64 on the device (df_flow_logpdf_wsum).  ``x`` (d, B), ``theta`` (n, B) or None, ``w``
+    (B,): host arrays or device tensors; host weights are checked first (:func:`check_weights`)."""
+    import torch
+
+    h = flow.hip()
+    dev = h.device
+    B = int(x.shape[1])
+    if not torch.is_tensor(w):
+        w = torch.from_numpy(check_weights(w, B)).to(dev)
+    elif w.dim() != 1 or int(w.shape[0]) != B:
+        raise _lib.ArgumentError(f"weights must have shape ({B},), one per sample; got {tuple(w.shape)}")
+    w = w.to(device=dev, dtype=torch.float32).contiguous()
+    xt = as_julia_device(x, flow.d, dev, "x")[0]
+    tt = as_julia_device(theta, flow.n, dev, "θ")[0] if flow.n > 0 else None
+    out = torch.zeros(2, dtype=torch.float64, device=dev)
+    h.run_logpdf_wsum(xt, tt, w, out, B)
+    s, W = (float(v) for v in out.cpu().numpy())
+    return (-s / W if W > 0 else float("nan")), W
+
+
 def _dense_order(elements):
     """Dense layers in Flux.trainables order (s_net then t_net per coupling layer)."""
     out = []
@@ -415,17 +507,38 @@ def _dist():
     return dist if dist.is_available() and dist.is_initialized() else None
 
 
-def _loss(flow, x, th, group=None, comm=None):
+def _loss(flow, x, th, group=None, comm=None, w=None):
     """loss(backward(model, x, θ)...) over a whole set (fused NLL, fp64 sum).
     With a ``DFComm`` the set is sharded over its ranks and reduced inside the
     library (df_flow_nll); under a bare torch.distributed group (the gloo
-    rehearsal) the 16-byte partial goes through torch."""
+    rehearsal) the 16-byte partial goes through torch.  ``w`` (host weights, one per
+    sample): the weighted mean ``-Σ w·logpdf / Σ w``, each rank's ``{Σ w·logpdf, Σ w}``
+    (df_flow_logpdf_wsum) summed over the ranks."""
     import torch
 
     from .parallel import allreduce_nll, flow_nll, shard_range
 
     B = x.shape[1]
     dist = _dist()
+    if w is not None:
+        if comm is not None:
+            a, b = shard_range(B, comm.rank, comm.world)
+        elif dist is not None:
+            a, b = shard_range(B, dist.get_rank(group), dist.get_world_size(group))
+        else:
+            a, b = 0, B
+        h = flow.hip()
+        s = torch.zeros(2, dtype=torch.float64, device=h.device)
+        if b > a:
+            xt = as_julia_device(x[:, a:b], flow.d, h.device, "x")[0]
+            tt = as_julia_device(th[:, a:b], flow.n, h.device, "θ")[0] if th is not None else None
+            h.run_logpdf_wsum(xt, tt, torch.from_numpy(np.ascontiguousarray(w[a:b], np.float32)).to(h.device), s, b - a)
+        if comm is not None:
+            comm.allreduce_(s)
+        elif dist is not None:
+            dist.all_reduce(s, op=dist.ReduceOp.SUM, group=group)
+        sw, W = (float(v) for v in s.cpu().numpy())
+        return -sw / W if W > 0 else float("nan")
     if comm is not None:
         a, b = shard_range(B, comm.rank, comm.world)
         return flow_nll(flow, x[:, a:b], th[:, a:b] if th is not None else None, comm)[0]
@@ -482,7 +595,14 @@ def train_(flow, data, state: TrainState, epochs: int = 100, batchsize: int = 64
     ``flow.train_loss`` and ``flow.valid_loss`` are bitwise the host loader's.
     ``return_step_losses`` (device loader only): the call returns ``(result, losses)``,
     ``result`` being what it returns otherwise and ``losses`` a float64 numpy array with the
-    loss ``-Σ logpdf / B`` of every mini-batch at the parameters before its step."""
+    loss ``-Σ logpdf / B`` of every mini-batch at the parameters before its step.
+
+    Sample weights: with ``DataArrays(..., weights=w)`` every step minimises the mini-batch's
+    ``-Σ w·logpdf / Σ w`` on the device (df_train_step_w and its captured / epoch forms) and
+    ``flow.train_loss`` / ``flow.valid_loss`` (and the step losses) are the weighted means.
+    Data-parallel ranks divide by the global mini-batch's ``Σ w``, taken in fp64 from the
+    host's copy, all-reduce the gradient and apply.  Data without weights takes the
+    unweighted calls."""
     if loader not in ("host", "device"):
         raise _lib.ArgumentError(f'loader must be "host" or "device", got {loader!r}')
     if loader == "device":
@@ -509,6 +629,10 @@ def train_(flow, data, state: TrainState, epochs: int = 100, batchsize: int = 64
     N = x_tr.shape[1]
     Xs = xt.view(N, flow.d)                                      # row j = sample j
     Ts = tt.view(N, n) if tt is not None else None
+    # sample weights (DataArrays(weights=)): the weighted loss on every path below; None:
+    # the unweighted calls, untouched
+    w_tr, w_va = _data_weights(data, N, x_va.shape[1])
+    Ws = torch.from_numpy(w_tr).to(dev) if w_tr is not None else None
     dist = _dist()
     if comm is not None:
         rank, world = comm.rank, comm.world
@@ -527,17 +651,37 @@ def train_(flow, data, state: TrainState, epochs: int = 100, batchsize: int = 64
                 if local and graphs:
                     if B not in staging:
                         staging[B] = (torch.empty((B, flow.d), dtype=Xs.dtype, device=dev),
-                                      torch.empty((B, n), dtype=Ts.dtype, device=dev) if Ts is not None else None)
-                    xb, tb = staging[B]
+                                      torch.empty((B, n), dtype=Ts.dtype, device=dev) if Ts is not None else None,
+                                      torch.empty(B, dtype=torch.float32, device=dev) if Ws is not None else None)
+                    xb, tb, wb = staging[B]
                     torch.index_select(Xs, 0, ii, out=xb)
                     if Ts is not None:
                         torch.index_select(Ts, 0, ii, out=tb)
-                    tr.step_graph(xb, tb, B)
+                    if Ws is not None:
+                        torch.index_select(Ws, 0, ii, out=wb)
+                    tr.step_graph(xb, tb, B, w=wb)
                     continue
                 xb = Xs.index_select(0, ii).contiguous()
                 tb = Ts.index_select(0, ii).contiguous() if Ts is not None else None
+                wb = Ws.index_select(0, ii).contiguous() if Ws is not None else None
                 if local:
-                    tr.step(xb, tb, B)
+                    tr.step(xb, tb, B, w=wb)
+                elif Ws is not None:
+                    # every rank divides by the global batch's Σ w (from the host's copy, in
+                    # fp64), so the shards' gradients add up to the global batch's
+                    w_total = float(np.sum(w_tr[idx], dtype=np.float64))
+                    sums = torch.zeros(2, dtype=torch.float64, device=dev)
+                    tr.gradient(xb, tb, b - a, w=wb, w_total=w_total, wsums=sums)
+                    if comm is not None:
+                        tr.allreduce_gradient(comm)
+                    else:
+                        dist.all_reduce(tr.grad(), op=dist.ReduceOp.SUM, group=group)
+                    if debug and dist is not None and comm is None:  # the rehearsal's loss check
+                        lp = sums[:1].clone()
+                        dist.all_reduce(lp, op=dist.ReduceOp.SUM, group=group)
+                        if _nonfinite(float(lp.item()) / w_total):
+                            raise _lib.NonFiniteError(f"non-finite training loss {-float(lp.item()) / w_total}")
+                    tr.apply()
                 elif comm is not None:
                     tr.step_dist(comm, xb, tb, b - a, B)
                 else:
@@ -563,14 +707,14 @@ def train_(flow, data, state: TrainState, epochs: int = 100, batchsize: int = 64
                     s = flow.hip().logpdf_sum(xv, tv)[0]
                     print(f"{-float(s.item()) / max(b - a, 1)}, {ldj.cpu().numpy()}, {z.cpu().numpy()}")
                 raise _lib.ArgumentError(str(e)) from e
-        train_loss = _loss(flow, x_tr, th_tr if n > 0 else None, group, comm)
+        train_loss = _loss(flow, x_tr, th_tr if n > 0 else None, group, comm, w_tr)
         flow.train_loss.append(train_loss)
         if debug and _nonfinite(train_loss):
             if rank == 0:
                 print(f"Problem with train loss {train_loss}")
             state.sync_model()
             return _backward_set(flow, x_tr, th_tr)
-        valid_loss = _loss(flow, x_va, th_va if n > 0 else None, group, comm)
+        valid_loss = _loss(flow, x_va, th_va if n > 0 else None, group, comm, w_va)
         flow.valid_loss.append(valid_loss)
         if debug and _nonfinite(valid_loss):
             if rank == 0:
@@ -581,6 +725,16 @@ def train_(flow, data, state: TrainState, epochs: int = 100, batchsize: int = 64
             print(f"epoch: {len(flow.train_loss)} | train_loss = {train_loss}, valid_loss = {valid_loss}")
     state.sync_model()
     return (None, None) if debug else None
+
+
+def _data_weights(data, n_train: int, n_valid: int):
+    """The training and validation weights of ``data`` as float32 host arrays, checked, or
+    ``(None, None)`` for data without weights."""
+    if getattr(data, "weights", None) is None:
+        return None, None
+    w_tr = check_weights(data.training_weights(), n_train, "training weights")
+    w_va = check_weights(data.validation_weights(), n_valid, "validation weights")
+    return w_tr, w_va
 
 
 def _train_device(flow, data, state: TrainState, epochs, batchsize, shuffle, verbose, debug, rng, return_step_losses):
@@ -605,6 +759,11 @@ def _train_device(flow, data, state: TrainState, epochs, batchsize, shuffle, ver
     N, Nv = x_tr.shape[1], x_va.shape[1]
     steps = -(-N // int(batchsize))
     order_dev = torch.empty(N, dtype=torch.int32, device=dev) if shuffle else None
+    w_tr, w_va = _data_weights(data, N, Nv)
+    if w_tr is not None:
+        return _train_device_w(flow, state, epochs, int(batchsize), shuffle, verbose, debug, rng, return_step_losses,
+                               (x_tr, th_tr, x_va, th_va), (xt, tt, xv, tv), torch.from_numpy(w_tr).to(dev),
+                               torch.from_numpy(w_va).to(dev), order_dev)
     # [Σ logpdf of every step | Σ over the training set | Σ over the validation set]: one copy per epoch
     sums = torch.zeros(steps + 2, dtype=torch.float64, device=dev)
     step_losses = []
@@ -640,6 +799,68 @@ def _train_device(flow, data, state: TrainState, epochs, batchsize, shuffle, ver
             step_losses.append(-got[:steps] / sizes)
         train_loss = -float(got[steps]) / float(N) if N > 0 else float("nan")
         valid_loss = -float(got[steps + 1]) / float(Nv) if Nv > 0 else float("nan")
+        flow.train_loss.append(train_loss)
+        if debug and _nonfinite(train_loss):
+            print(f"Problem with train loss {train_loss}")
+            state.sync_model()
+            return ret(_backward_set(flow, x_tr, th_tr))
+        flow.valid_loss.append(valid_loss)
+        if debug and _nonfinite(valid_loss):
+            print(f"Problem with valid loss {valid_loss}")
+            state.sync_model()
+            return ret(_backward_set(flow, x_va, th_va))
+        if verbose:
+            print(f"epoch: {len(flow.train_loss)} | train_loss = {train_loss}, valid_loss = {valid_loss}")
+    state.sync_model()
+    return ret((None, None) if debug else None)
+
+
+def _train_device_w(flow, state, epochs, batchsize, shuffle, verbose, debug, rng, return_step_losses, host, dev_sets,
+                    wt, wv, order_dev):
+    """The device loader on a weighted set: the weights resident beside x and θ, gathered per
+    step (``df_train_epoch_w``); every sum below comes as the pair ``{Σ w·logpdf, Σ w}``."""
+    import torch
+
+    x_tr, th_tr, x_va, th_va = host
+    xt, tt, xv, tv = dev_sets
+    tr = state.trainer
+    dev = tr.device
+    n = flow.n
+    h = flow.hip()
+    N, Nv = x_tr.shape[1], x_va.shape[1]
+    steps = -(-N // batchsize)
+    # [{Σ w·lp, W} of every step | of the training set | of the validation set]: one copy per epoch
+    sums = torch.zeros(2 * (steps + 2), dtype=torch.float64, device=dev)
+    step_losses = []
+    ret = lambda r: (r, np.concatenate(step_losses) if step_losses else np.zeros(0)) if return_step_losses else r
+    for _ in range(epochs):
+        order = rng.permutation(N) if shuffle else None
+        if shuffle:
+            order_dev.copy_(torch.from_numpy(order.astype(np.int32)))
+        try:
+            tr.epoch(xt, tt, N, order_dev, batchsize, w=wt, step_wsums=sums[:2 * steps] if steps else None)
+        except _lib.NonFiniteError as e:
+            state.sync_model()
+            b0 = tr.steps_done * batchsize
+            idx = order[b0:b0 + batchsize] if shuffle else np.arange(b0, min(b0 + batchsize, N))
+            ii = torch.as_tensor(idx, device=dev)
+            xb = xt.view(N, flow.d).index_select(0, ii)
+            tb = tt.view(N, n).index_select(0, ii) if tt is not None else None
+            xv_, tv_ = xb.T, (tb.T if tb is not None else None)
+            z, ldj = flow.backward(xv_, tv_)
+            loss, _ = weighted_nll(flow, xv_, tv_, wt.index_select(0, ii))
+            print(f"{loss}, {ldj.cpu().numpy()}, {z.cpu().numpy()}")
+            raise _lib.ArgumentError(str(e)) from e
+        sums[2 * steps:].zero_()
+        if N > 0:
+            h.run_logpdf_wsum(xt, tt, wt, sums[2 * steps:2 * steps + 2], N)
+        if Nv > 0:
+            h.run_logpdf_wsum(xv, tv, wv, sums[2 * steps + 2:], Nv)
+        got = sums.cpu().numpy().reshape(steps + 2, 2)
+        if return_step_losses:
+            step_losses.append(-got[:steps, 0] / got[:steps, 1])
+        train_loss = -float(got[steps, 0]) / float(got[steps, 1]) if N > 0 else float("nan")
+        valid_loss = -float(got[steps + 1, 0]) / float(got[steps + 1, 1]) if Nv > 0 else float("nan")
         flow.train_loss.append(train_loss)
         if debug and _nonfinite(train_loss):
             print(f"Problem with train loss {train_loss}")

@@ -511,6 +511,58 @@ int df_batch_gather(float* x_out, float* theta_out, const float* x_set, const fl
  * n_samples >= 2^31: DF_ERR_SHAPE.  Not for data parallelism (df_train_step_dist). */
 int df_train_epoch(df_train* t, const float* x_set, const float* theta_set, int64_t n_samples, const int32_t* order,
                    int64_t batchsize, double* step_logpdf_sum, int64_t* steps_done, void* stream);
+/* ---- sample weights (additive to ABI 5) ----------------------------------------
+ * The weighted loss of one mini-batch,  loss_w = -Σ_i w_i·logpdf_i / W,  W = Σ_i w_i:
+ * for nested-sampling and importance-sampling chains, reweighted simulations, event
+ * weights.  w is a device float[batch]; wsums a device double[2] that receives
+ * {Σ_i w_i·logpdf_i, W} (may be NULL); the loss is -wsums[0] / wsums[1].
+ *   W      summed in fp64 in a fixed order on the device (w_total == 0), or w_total as
+ *          given (w_total > 0: data-parallel shards pass the global sum, so the shards'
+ *          gradients add up to the global batch's gradient);
+ *   inv_W  = 1.f / (float)W, so that w ≡ 1 gives 1.f / (float)batch bit for bit: with unit
+ *          weights the gradient is bitwise df_train_gradient's with n_total = batch;
+ *   wj_i   = w_i · inv_W in Float32 is the only form of the weights the sweep sees
+ *          (z̄_i = z_i·wj_i, j̄_i = wj_i): scaling every weight by a power of two changes
+ *          no bit of the gradient;
+ *   Σw·lp  summed in fp64 in a fixed order over the per-sample Float32 logpdf.
+ * NOT checked (a check would synchronise, as for df_batch_gather's order): the weights
+ * are expected finite and >= 0 with W > 0.  A zero-weight sample must still have finite
+ * x and θ (0·NaN is NaN).  W <= 0 or a non-finite weight gives a non-finite loss and
+ * gradient; under df_train_set_debug such a step is refused with DF_ERR_NONFINITE (the
+ * read-back divides by W).  Nothing past `batch` entries of x, θ or w is read.
+ * w_total negative or NaN, or w == NULL with batch > 0: DF_ERR_INVALID.
+ * batch == 0: zero gradient, zero wsums.
+ * df_train_step_w: gradient_w (w_total = 0) + df_train_apply.
+ * df_train_step_graph_w: that step as one hipGraph, as df_train_step_graph; the capture is
+ * keyed by (x, θ, w, batch, w_total, wsums).  W is recomputed inside the graph, so
+ * rewriting the weight buffer between replays is honoured. */
+int df_train_gradient_w(df_train* t, const float* x, const float* theta_raw, const float* w, int64_t batch,
+                        double w_total, double* wsums, void* stream);
+int df_train_step_w(df_train* t, const float* x, const float* theta_raw, const float* w, int64_t batch,
+                    double* wsums, void* stream);
+int df_train_step_graph_w(df_train* t, const float* x, const float* theta_raw, const float* w, int64_t batch,
+                          double w_total, double* wsums, void* stream);
+/* df_batch_gather with the set's weights: also w_out[j] = w_set[order[first + j]], in the
+ * same launch.  Every rule of df_batch_gather holds (a bad order entry gathers sample 0 of
+ * all three arrays). */
+int df_batch_gather_w(float* x_out, float* theta_out, float* w_out, const float* x_set, const float* theta_set,
+                      const float* w_set, int d, int n, int64_t n_samples, const int32_t* order, int64_t first,
+                      int64_t count, void* stream);
+/* df_train_epoch with sample weights (w_set: device float[n_samples]): step i is
+ * df_train_step_w on its mini-batch with the gathered weights, W being that mini-batch's
+ * own sum.  step_wsums (device, 2 doubles per step, may be NULL) receives every step's
+ * {Σ w·logpdf, W}.  Every rule of df_train_epoch holds; the weighted steps are captured in
+ * graph slots of their own. */
+int df_train_epoch_w(df_train* t, const float* x_set, const float* theta_set, const float* w_set, int64_t n_samples,
+                     const int32_t* order, int64_t batchsize, double* step_wsums, int64_t* steps_done, void* stream);
+/* wsums[0..1] = {Σ_j w_j·logpdf_j, Σ_j w_j} over a batch, both in fp64 in a fixed order
+ * (the epoch losses of a weighted set: -wsums[0] / wsums[1]).  df_flow_*: θ raw;
+ * df_chain_*: θ as given.  batch == 0 zeroes wsums.  The per-sample logpdf goes through a
+ * workspace the chain owns (it only grows). */
+int df_flow_logpdf_wsum(df_chain* chain, const float* x, const float* theta_raw, const float* w, int64_t batch,
+                        double* wsums, void* stream);
+int df_chain_logpdf_wsum(df_chain* chain, const float* x, const float* theta, const float* w, int64_t batch,
+                         double* wsums, void* stream);
 /* train!(...; debug=true) (src/Flows.jl:404-409): when on, df_train_apply
  * (and the steps built on it) first reads the Σ logpdf of the last gradient
  * evaluation back to the host; if the loss is NaN or ±Inf the parameters are
