@@ -623,11 +623,10 @@ __device__ __forceinline__ void split_step_request(const uint8_t* wl, const uint
 // first step so precedes that chunk's activation split.  f0 = step 0, requested by the
 // caller.
 template <int HT, int TT, bool BIAS = true>
-__device__ __forceinline__ void dense_hidden_split_pf(const uint8_t* wb, int lane, const f32x4 (&in)[TT][HT],
+__device__ __forceinline__ void dense_hidden_split_pf(const uint8_t* wb, int l16, int g16, const f32x4 (&in)[TT][HT],
                                                       f32x4 (&out)[TT][HT], const SplitStep& f0) {
-    const int g = lane >> 4;
-    const uint8_t* bl = wb + (HT / 2) * HT * 3072 + (g << 4);
-    const uint8_t* wl = wb + lane * 16;
+    const uint8_t* bl = wb + (HT / 2) * HT * 3072 + g16;
+    const uint8_t* wl = wb + l16;
     const short4v eye = neg_eye();
     SplitStep f[2];
     f[0] = f0;
@@ -676,11 +675,16 @@ __device__ __forceinline__ void dense_first_split_pf(const bf16x8 (&w)[HT], cons
     bf16x8 b[TT];
     const __bf16 z = (__bf16)0.f;
 #pragma unroll
-    for (int t = 0; t < TT; t += 2) {  // tiles in pairs: one split of two values
+    for (int t = 0; t < TT; ++t) {
+        // one value per tile, split on its own: each plane is the low half of its
+        // conversion, so a remainder takes a shift and a subtract (a pair of two tiles'
+        // values needs a mask for the high half as well); the planes are split2's
         bf16x2 h, m, l;
-        split2(xin[t][0], t + 1 < TT ? xin[t + 1][0] : 0.f, h, m, l);
+        h = bf16x2{(__bf16)xin[t][0], z};
+        const float r1 = split_rem<0>(h, xin[t][0]);
+        m = bf16x2{(__bf16)r1, z};
+        l = bf16x2{(__bf16)split_rem<0>(m, r1), z};
         b[t] = bf16x8{h[0], m[0], h[0], l[0], m[0], h[0], z, z};
-        if (t + 1 < TT) b[t + 1] = bf16x8{h[1], m[1], h[1], l[1], m[1], h[1], z, z};
     }
 #pragma unroll
     for (int m = 0; m < HT; ++m)
@@ -696,16 +700,42 @@ __device__ __forceinline__ void out_row_request(const uint8_t* w3g, int oo, f32x
     for (int kq = 0; kq < HT; ++kq) w[kq] = lds4(w3g + ((oo * 16 * HT + 16 * kq) << 2));
 }
 
+// How many (row, output) pairs a lane group owns after the tail's transposed reduction.
+// The reduction has four slots.  A group of two tiles with NO <= 2 outputs fills them with
+// BOTH tiles' outputs, so one tree, one coupling and one ldj update serve the two tiles:
+//   NO = 2: lane group g owns output g & 1 of tile g >> 1;
+//   NO = 1: lane group g owns the output of tile g & 1 (groups 2, 3 hold copies of 0, 1:
+//           they compute and store the same bits to the same words, no lane is masked).
+// Otherwise every tile has its own tree and group g owns output g of each of the TT tiles.
+constexpr int split_tail_rows(int TT, int NO) { return (TT == 2 && NO <= 2) ? 1 : TT; }
+
+// What a read-ahead SPLIT body and the ldj update behind it (uniform_kernel's tiles_loop)
+// share: ce, the state column of ldj_elem (ldj_chain is the column before it), goes in;
+// per owned row u the row's offset and its two ldj words as they stood before the body
+// (requested with the coupling's old values, so no round trip of their own) come out.
+// l16, g16: the lane's two offsets into fragments and vectors, lane · 16 and (lane >> 4) · 16,
+// from the kernel where the instance has the registers to hold them across bodies (LANES
+// of net_tiles); otherwise the body derives them from an opaque copy of the thread id.
+template <int TT>
+struct SplitTail {
+    int ce, l16, g16;
+    int row[TT];
+    float e_old[TT], a_old[TT];
+};
+
 // out_valu_t on two sets of weight vectors: output 0's (w0, with the bias bo and the
 // coupling's slot word) were requested by the caller before the second relu; output
 // oo + 1's are requested ahead of output oo's 4·HT·TT fma, the coupling's old state
-// values (state[ro[t] + aslot] -> v) with output 1's.  fma order (oo, kq, r) and the swap
-// reduction as in out_valu_t.
-template <int HT, int TT, int NO>
+// values (state[row[u] + aslot] -> v) and, LDJ, the rows' ldj words (tl) with output 1's.
+// fma order (oo, kq, r) as in out_valu_t; the swap reduction as in out_valu_t per tile, or
+// one tree for both tiles (split_tail_rows): every sum still associates
+// ((p_g0 + p_g1) + (p_g2 + p_g3)), as outputs 2, 3 of a four-output net do in their slots.
+template <int HT, int TT, int NO, bool LDJ, int NU>
 __device__ __forceinline__ void out_valu_t_pf(const uint8_t* w3g, const f32x4 (&w0)[HT], float bo,
-                                              const f32x4 (&h)[TT][HT], const float* state, const int (&ro)[TT],
-                                              const int& aslot, float (&v)[TT], float (&y)[TT]) {
+                                              const f32x4 (&h)[TT][HT], const float* state, const int& aslot,
+                                              SplitTail<TT>& tl, float (&v)[NU], float (&y)[NU]) {
     static_assert(NO >= 1 && NO <= 4, "FAST tails: 1..4 outputs");
+    static_assert(NU == split_tail_rows(TT, NO), "rows a lane group owns");
     float p[TT][4];
 #pragma unroll
     for (int t = 0; t < TT; ++t)
@@ -720,7 +750,13 @@ __device__ __forceinline__ void out_valu_t_pf(const uint8_t* w3g, const f32x4 (&
         lds_wait0();
         if (oo == 0) {
 #pragma unroll
-            for (int t = 0; t < TT; ++t) v[t] = state[ro[t] + aslot];
+            for (int u = 0; u < NU; ++u) {
+                v[u] = state[tl.row[u] + aslot];
+                if constexpr (LDJ) {  // a word whose value the update does not use is read for nothing
+                    tl.e_old[u] = state[tl.row[u] + tl.ce];
+                    tl.a_old[u] = state[tl.row[u] + tl.ce - 1];
+                }
+            }
         }
         out_row_request<HT, NO>(w3g, oo + 1, w[(oo + 1) & 1]);
         sched_fence();
@@ -734,17 +770,30 @@ __device__ __forceinline__ void out_valu_t_pf(const uint8_t* w3g, const f32x4 (&
 #pragma unroll
         for (int t = 0; t < TT; ++t) asm volatile("" : "+v"(p[t][oo]));
     }
-#pragma unroll
-    for (int t = 0; t < TT; ++t) {
-        auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(p[t][0]), __float_as_uint(p[t][1]), false, false);
-        const float A = __uint_as_float(a[0]) + __uint_as_float(a[1]);  // rows: p0 g01, p1 g01, p0 g23, p1 g23
-        float Bv = 0.f;
-        if constexpr (NO > 2) {
-            auto b = __builtin_amdgcn_permlane16_swap(__float_as_uint(p[t][2]), __float_as_uint(p[t][3]), false, false);
-            Bv = __uint_as_float(b[0]) + __uint_as_float(b[1]);             // p2 g01, p3 g01, p2 g23, p3 g23
+    if constexpr (NU < TT) {  // one tree: the slots hold both tiles
+        const float q = NO == 2 ? p[0][1] : p[1][0];
+        auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(p[0][0]), __float_as_uint(q), false, false);
+        const float A = __uint_as_float(a[0]) + __uint_as_float(a[1]);  // NO = 2, tile 0: p0 g01, p1 g01, p0 g23, p1 g23
+        float Bv = A;                                                     // NO = 1: t0 g01, t1 g01, t0 g23, t1 g23
+        if constexpr (NO == 2) {
+            auto b = __builtin_amdgcn_permlane16_swap(__float_as_uint(p[1][0]), __float_as_uint(p[1][1]), false, false);
+            Bv = __uint_as_float(b[0]) + __uint_as_float(b[1]);           // tile 1: p0 g01, p1 g01, p0 g23, p1 g23
         }
         auto c = __builtin_amdgcn_permlane32_swap(__float_as_uint(A), __float_as_uint(Bv), false, false);
-        y[t] = (__uint_as_float(c[0]) + __uint_as_float(c[1])) + bo;      // group g: output g
+        y[0] = (__uint_as_float(c[0]) + __uint_as_float(c[1])) + bo;      // split_tail_rows: the group's (tile, output)
+    } else {
+#pragma unroll
+        for (int t = 0; t < TT; ++t) {
+            auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(p[t][0]), __float_as_uint(p[t][1]), false, false);
+            const float A = __uint_as_float(a[0]) + __uint_as_float(a[1]);  // rows: p0 g01, p1 g01, p0 g23, p1 g23
+            float Bv = 0.f;
+            if constexpr (NO > 2) {
+                auto b = __builtin_amdgcn_permlane16_swap(__float_as_uint(p[t][2]), __float_as_uint(p[t][3]), false, false);
+                Bv = __uint_as_float(b[0]) + __uint_as_float(b[1]);             // p2 g01, p3 g01, p2 g23, p3 g23
+            }
+            auto c = __builtin_amdgcn_permlane32_swap(__float_as_uint(A), __float_as_uint(Bv), false, false);
+            y[t] = (__uint_as_float(c[0]) + __uint_as_float(c[1])) + bo;      // group g: output g
+        }
     }
 }
 
@@ -781,9 +830,13 @@ __device__ __forceinline__ void split_prio() {
 // Evaluate net N for TT 16-sample tiles (state rows ro[t]) and apply its
 // coupling phase; sum[t] = Σ_k s_k for s phases (row order).
 // hd: the read-ahead SPLIT path's scalar words (SplitHead); unused by every other path.
-template <int HT, int TT, bool OUTV, bool RELU, int PH, bool FAST = false, int NO = 0, bool SPLIT = false>
+// tl, LDJ: that path's tail (SplitTail); there sum[u] belongs to row tl.row[u],
+// u < split_tail_rows(TT, NO), and LDJ asks an s phase for the rows' ldj words.
+template <int HT, int TT, bool OUTV, bool RELU, int PH, bool FAST = false, int NO = 0, bool SPLIT = false,
+          bool LDJ = false, bool LANES = false>
 __device__ __forceinline__ void net_tiles(const uint8_t* buf, const UNet& N, const ULayer& L, const int32_t* tab,
-                                          float* state, const int (&ro)[TT], float (&sum)[TT], const SplitHead& hd) {
+                                          float* state, const int (&ro)[TT], float (&sum)[TT], const SplitHead& hd,
+                                          SplitTail<TT>& tl) {
     const int lane = threadIdx.x & 63, g = lane >> 4;
     constexpr bool SPH = (PH == impl::PH_S_FWD || PH == impl::PH_S_BWD);
 #if DF_SPLIT_HEAD_REGS
@@ -797,23 +850,28 @@ __device__ __forceinline__ void net_tiles(const uint8_t* buf, const UNet& N, con
         // extract.  (With the table word in LDS and every offset a scalar load at its use,
         // a body made five dependent round trips before its first MFMA:
         // profiles/head_isa_waits.txt.)
-        // lane and g from an opaque copy of the thread id: derived here they die with the
-        // body; derived once per kernel every lane offset is a VGPR held across all bodies,
-        // which this instance (128 VGPRs) does not have
-        int tx = threadIdx.x;
-        asm volatile("" : "+v"(tx));
-        const int lane = tx & 63, g = lane >> 4;
+        // l16 and g16 from an opaque copy of the thread id: derived here they die with the
+        // body; derived once per kernel (LANES) they are two VGPRs held across all bodies,
+        // which the logpdf instances (past 120 of 128 VGPRs) do not have
+        int l16 = tl.l16, g16 = tl.g16;
+        if constexpr (!LANES) {
+            int tx = threadIdx.x;
+            asm volatile("" : "+v"(tx));
+            l16 = (tx & 63) << 4, g16 = tx & 48;
+        }
+        const int g = g16 >> 4;
         const uint8_t* net = buf + hd.off_w0;
-        const int slot = ((uint32_t)hd.feat_word >> (kSplitSlotBits * g)) & ((1 << kSplitSlotBits) - 1);
+        const int slot = ((uint32_t)hd.feat_word >> (g16 >> 1)) & ((1 << kSplitSlotBits) - 1);
+        static_assert(kSplitSlotBits == 8, "slot of lane group g at bit 8 g = g16 / 2");
         bf16x8 w0[HT];
 #pragma unroll
-        for (int m = 0; m < HT; ++m) w0[m] = *reinterpret_cast<const bf16x8*>(net + lane * 16 + m * 1024);
+        for (int m = 0; m < HT; ++m) w0[m] = *reinterpret_cast<const bf16x8*>(net + l16 + m * 1024);
         float xin[TT][4];
 #pragma unroll
         for (int t = 0; t < TT; ++t) xin[t][0] = state[ro[t] + slot];
         const uint8_t* wh = net + kSplitOffH(HT);
         SplitStep f0;
-        split_step_request<HT, true>(wh + lane * 16, wh + (HT / 2) * HT * 3072 + (g << 4), 0, f0);
+        split_step_request<HT, true>(wh + l16, wh + (HT / 2) * HT * 3072 + g16, 0, f0);
         sched_fence();
         lds_wait0();
         split_prio<true>();
@@ -821,24 +879,52 @@ __device__ __forceinline__ void net_tiles(const uint8_t* buf, const UNet& N, con
         f32x4 A[TT][HT], B[TT][HT];
         dense_first_split_pf<HT, TT>(w0, xin, A);
         bias_act<HT, TT, true>(buf, DF_ACT_RELU, A, false);
-        dense_hidden_split_pf<HT, TT>(wh, lane, A, B, f0);
+        dense_hidden_split_pf<HT, TT>(wh, l16, g16, A, B, f0);
         // tail: the first output's weights and the bias before the second relu
         const uint8_t* w3 = net + kSplitOffOut(HT);
-        const uint8_t* w3g = w3 + (g << 4);
+        const uint8_t* w3g = w3 + g16;
         sched_fence();
         split_prio<false>();
         f32x4 wo[HT];
         out_row_request<HT, NO>(w3g, 0, wo);
-        const float bo = reinterpret_cast<const float*>(w3)[NO * 16 * HT + (g < NO ? g : 0)];
-        const int aslot = ((uint32_t)hd.af_word >> (kSplitSlotBits * g)) & ((1 << kSplitSlotBits) - 1);
+        // the (row, output) this lane group owns after the reduction (split_tail_rows)
+        constexpr int NU = split_tail_rows(TT, NO);
+        constexpr bool ONE_TREE = NU < TT;
+        const int go = ONE_TREE ? (NO == 2 ? (g & 1) : 0) : (g < NO ? g : 0);
+        const float bo = reinterpret_cast<const float*>(w3)[NO * 16 * HT + go];
+        const int aslot = ((uint32_t)hd.af_word >> (kSplitSlotBits * go)) & ((1 << kSplitSlotBits) - 1);
+        if constexpr (ONE_TREE) {
+            // (an offset, not a choice between ro[0] and ro[1]: that is an indexed read of
+            // ro, which then lives in scratch)
+            tl.row[0] = ro[0] + ((NO == 2 ? (g >> 1) : (g & 1)) ? ro[1] - ro[0] : 0);
+        } else {
+#pragma unroll
+            for (int t = 0; t < TT; ++t) tl.row[t] = ro[t];
+        }
         sched_fence();
         bias_act<HT, TT, true>(buf, DF_ACT_RELU, B, false);
-        float v[TT], y[TT];
-        out_valu_t_pf<HT, TT, NO>(w3g, wo, bo, B, state, ro, aslot, v, y);
+        float v[NU], y[NU];
+        out_valu_t_pf<HT, TT, NO, SPH && LDJ>(w3g, wo, bo, B, state, aslot, tl, v, y);
+        // one region for the lane groups that own an output (all of them with one tree), so
+        // that the tiles' couplings interleave
+        if (ONE_TREE || g < NO) {
 #pragma unroll
-        for (int t = 0; t < TT; ++t) {
-            if (g < NO) state[ro[t] + aslot] = couple1<PH>(v[t], y[t]);
-            sum[t] = SPH ? group_row_sum<NO>(y[t]) : 0.f;  // valid in lane group 0 (ldj_update)
+            for (int u = 0; u < NU; ++u) state[tl.row[u] + aslot] = couple1<PH>(v[u], y[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+            if constexpr (!SPH) {
+                sum[u] = 0.f;
+            } else if constexpr (ONE_TREE && NO == 2) {
+                // y_0 + y_1 of the group's tile, in all four lane groups: the row's ldj update
+                // needs no mask (group_row_sum's y + a[1] in groups 0 and 2, where y = a[0])
+                auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(y[u]), __float_as_uint(y[u]), false, false);
+                sum[u] = __uint_as_float(a[0]) + __uint_as_float(a[1]);
+            } else if constexpr (ONE_TREE) {
+                sum[u] = y[u];
+            } else {
+                sum[u] = group_row_sum<NO>(y[u]);  // valid in lane group 0
+            }
         }
         return;
     }
@@ -1092,6 +1178,14 @@ uniform_kernel(ChainArgs a) {
 #endif
     const int tstep = 16 * stride;
     bool have_acc = false;
+    // read-ahead SPLIT bodies: the lane's two fragment offsets as values held across all
+    // bodies (SplitTail).  What the compiler then hoists out of the bodies costs some ten
+    // VGPRs: the hidden-64 forward instances have them (117 -> 125, 114 -> 123 of 128); the
+    // inverse and logpdf instances (123, 125) would spill, and the hidden-32 instances would
+    // lose their fifth wave (90 -> 100 VGPRs)
+    constexpr bool kHoldLanes = kSplitHead && HT == 4 && FWD;
+    int lane16 = lane << 4, group16 = g << 4;
+    if constexpr (kHoldLanes) asm volatile("" : "+v"(lane16), "+v"(group16));
 
     auto ldj_update = [&](int ro, float l, bool first_in_elem, bool last_in_elem) {
         if (!WANT_LDJ || g != 0) return;
@@ -1169,11 +1263,35 @@ uniform_kernel(ChainArgs a) {
                     if constexpr (SPLIT) asm volatile("" : "+v"(r0));
 #pragma unroll
                     for (int t = 0; t < kTT; ++t) ro[t] = r0 + (tt + t) * tstep;
-                    net_tiles<HT, kTT, OUTV, RELU, PH, FAST, NO, SPLIT>(buf, N, L, tab, state, ro, ssum, hd);
+                    SplitTail<kTT> tl;
+                    tl.ce = cE, tl.l16 = lane16, tl.g16 = group16;
+                    net_tiles<HT, kTT, OUTV, RELU, PH, FAST, NO, SPLIT, WANT_LDJ, kHoldLanes>(buf, N, L, tab, state, ro,
+                                                                                              ssum, hd, tl);
+                    constexpr bool SPH = (PH == impl::PH_S_FWD || PH == impl::PH_S_BWD);
+                    if constexpr (kSplitHead && NO > 0 && SPH) {
+                        // ldj_update on the words the body read with the coupling's old values:
+                        // the same additions in the same order, the three uniform flags select
+                        // between values, and no LDS round trip stands between read and write.
+                        // One tree for both tiles: every lane group holds its row's Σ s, so all
+                        // lanes store (copies write the same bits); else lane group 0 does.
+                        constexpr int NU = split_tail_rows(kTT, NO);
+                        if constexpr (WANT_LDJ) {
+                            if (NU < kTT || g == 0) {
 #pragma unroll
-                    for (int t = 0; t < kTT; ++t) {
-                        if (sphase) ldj_update(ro[t], sign * ssum[t], first_in_elem, last_in_elem);
-                        else if (!rnvp) ldj_update(ro[t], 0.f, first_in_elem, last_in_elem);
+                                for (int u = 0; u < NU; ++u) {
+                                    const float l = sign * ssum[u];
+                                    const float e = first_in_elem ? l : tl.e_old[u] + l;
+                                    state[tl.row[u] + cE] = e;
+                                    if (last_in_elem) state[tl.row[u] + cA] = have_acc ? tl.a_old[u] + e : e;
+                                }
+                            }
+                        }
+                    } else {
+#pragma unroll
+                        for (int t = 0; t < kTT; ++t) {
+                            if (sphase) ldj_update(ro[t], sign * ssum[t], first_in_elem, last_in_elem);
+                            else if (!rnvp) ldj_update(ro[t], 0.f, first_in_elem, last_in_elem);
+                        }
                     }
                 }
             };
