@@ -143,6 +143,11 @@ struct df_chain {
     // [wlp_cap]) and the span sums of the fp64 reductions; they only grow
     DevBuf d_wlp, d_wlp_part;
     int64_t wlp_cap = 0;
+    // df_moments.hip; capacities in bytes, they only grow.  df_flow_sample_logpdf: the forward
+    // pass's ldj (float [batch]).  df_flow_sample_logpdf_moments: one chunk's x (d, chunk) and
+    // lp (chunk), and the reduction's per-workgroup blocks (double [workgroups][3])
+    DevBuf d_slp_ldj, d_mom_x, d_mom_lp, d_mom_part;
+    int64_t slp_ldj_cap = 0, mom_x_cap = 0, mom_lp_cap = 0, mom_part_cap = 0;
     ~df_chain() {
         if (d_theta_ws) (void)hipFree(d_theta_ws);
     }
@@ -190,6 +195,14 @@ constexpr double kLog2Pi = 1.8378770664093453;  // log(2π)
 int train_device(const df_train* t);
 // Device double the last df_train_gradient wrote Σ logpdf to (the caller's or the handle's own).
 double* train_last_lpsum(df_train* t);
+
+// df_flow_sample's θ checks (df_sample.hip): raw θ present and bounds set when n > 0.
+int sample_check_theta(const df_chain* c, const float* theta_raw);
+// df_flow_sample between those checks and its forward pass: the draw into x_out and, for
+// theta_broadcast, the θ broadcast into the chain's workspace.  *theta_use is the (n, batch)
+// θ the pass reads.  batch > 0; the caller holds the device.
+int sample_draw(df_chain* c, float* x_out, const float* theta_raw, int theta_broadcast, int64_t batch, uint64_t seed,
+                uint64_t offset, void* stream, const float** theta_use);
 
 // Launch one fused chain pass.  flow: θ normalised with the handle's bounds;
 // snap (inverse modes, specialised kernel): every layer's output kept.

@@ -114,12 +114,31 @@ int df_flow_sample(df_chain* c, float* x_out, const float* theta_raw, int theta_
     if (batch < 0) return set_err(DF_ERR_SHAPE, "negative batch size");
     if (batch == 0) return DF_OK;
     if (!x_out) return set_err(DF_ERR_INVALID, "null output array");
-    const int d = c->plan.d, n = c->plan.n;
-    if (n > 0 && !theta_raw)
-        return set_err(DF_ERR_SHAPE, "dimensions θ must match (n, dims...) with n number of trained parameters");
-    if (n > 0 && !c->has_bounds) return set_err(DF_ERR_INVALID, "θ bounds not set (df_chain_set_theta_bounds)");
+    int rc = sample_check_theta(c, theta_raw);
+    if (rc != DF_OK) return rc;
     DeviceGuard gd(c->device);
     if (!gd.ok) return set_err(DF_ERR_HIP, "hipSetDevice failed");
+    const float* th = nullptr;
+    rc = sample_draw(c, x_out, theta_raw, theta_broadcast, batch, seed, offset, stream, &th);
+    return rc != DF_OK ? rc : df_flow_forward_inplace(c, x_out, th, batch, stream);
+}
+
+}  // extern "C"
+
+namespace df {
+namespace api {
+
+int sample_check_theta(const df_chain* c, const float* theta_raw) {
+    if (c->plan.n > 0 && !theta_raw)
+        return set_err(DF_ERR_SHAPE, "dimensions θ must match (n, dims...) with n number of trained parameters");
+    if (c->plan.n > 0 && !c->has_bounds)
+        return set_err(DF_ERR_INVALID, "θ bounds not set (df_chain_set_theta_bounds)");
+    return DF_OK;
+}
+
+int sample_draw(df_chain* c, float* x_out, const float* theta_raw, int theta_broadcast, int64_t batch, uint64_t seed,
+                uint64_t offset, void* stream, const float** theta_use) {
+    const int d = c->plan.d, n = c->plan.n;
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = df::launch_normal(x_out, (int64_t)d * batch, seed, offset, st);
     if (e != hipSuccess) return hip_err(e, "normal_kernel launch");
@@ -145,7 +164,9 @@ int df_flow_sample(df_chain* c, float* x_out, const float* theta_raw, int theta_
         if ((e = hipGetLastError()) != hipSuccess) return hip_err(e, "broadcast_kernel launch");
         th = c->d_theta_ws;
     }
-    return df_flow_forward_inplace(c, x_out, th, batch, stream);
+    *theta_use = th;
+    return DF_OK;
 }
 
-}  // extern "C"
+}  // namespace api
+}  // namespace df

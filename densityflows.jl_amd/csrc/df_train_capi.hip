@@ -549,18 +549,25 @@ int df_train_logpdf_grad(df_train* t, const float* x, const float* theta, float*
                        "(a conditioner with hidden width > 64, more than one hidden Dense, or more than 4 "
                        "transformed dims in a layer)");
     if (batch == 0) return DF_OK;
+    DeviceGuard gd(t->c->device);
+    if (!gd.ok) return set_err(DF_ERR_HIP, "hipSetDevice failed");
+    return score_sweep(t, x, theta, logpdf_out, grad_x, grad_theta, batch, -1, static_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"
+
+int df::api::score_sweep(df_train* t, const float* x, const float* theta, float* logpdf_out, float* grad_x,
+                         float* grad_theta, int64_t batch, int flow_req, hipStream_t st) {
+    void* const stream = st;
     if (!x) return set_err(DF_ERR_INVALID, "null input array");
     df_chain* c = t->c;
     const Plan& P = c->plan;
     if (P.n > 0 && !theta)
         return set_err(DF_ERR_SHAPE, "dimensions θ must match (n, dims...) with n number of trained parameters");
-    const int tf = theta_flow(t);
+    const int tf = P.n == 0 ? 0 : flow_req >= 0 ? (flow_req == 1 && !c->has_bounds ? -1 : flow_req) : theta_flow(t);
     if (tf < 0) return set_err(DF_ERR_INVALID, "θ bounds not set (df_chain_set_theta_bounds) for DF_THETA_RAW");
     const bool flow = tf == 1;
     if (P.n == 0) grad_theta = nullptr;
-    DeviceGuard gd(c->device);
-    if (!gd.ok) return set_err(DF_ERR_HIP, "hipSetDevice failed");
-    hipStream_t st = static_cast<hipStream_t>(stream);
     if (!grad_x && !grad_theta) {  // logpdf alone: the inverse pass without the kept outputs
         if (!logpdf_out) return DF_OK;
         return run(c, MODE_LOGPDF, flow, x, theta, nullptr, nullptr, logpdf_out, nullptr, batch, stream);
@@ -645,6 +652,8 @@ int df_train_logpdf_grad(df_train* t, const float* x, const float* theta, float*
     }
     return DF_OK;
 }
+
+extern "C" {
 
 int df_train_apply(df_train* t, void* stream) {
     if (!t) return set_err(DF_ERR_INVALID, "null trainer");

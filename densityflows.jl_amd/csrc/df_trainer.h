@@ -136,6 +136,12 @@ struct df_train {
     EpochKey ekeyw;
     StepGraph egw[2];
     int64_t egw_count[2] = {0, 0};
+    // df_train_score_moments / df_train_fisher (df_moments.hip); capacities in bytes, they only
+    // grow: the sweep's lp (float [batch]) and gθ (n, batch), the reduction's per-workgroup
+    // blocks (double [workgroups][3 + n + n²]), and one chunk's draws x (d, chunk) with the θ
+    // broadcast (n, chunk)
+    DevBuf d_mom_lp, d_mom_g, d_mom_part, d_mom_x, d_mom_th;
+    int64_t mom_lp_cap = 0, mom_g_cap = 0, mom_part_cap = 0, mom_x_cap = 0, mom_th_cap = 0;
 };
 
 // the H0-free sweep is planned and its buffers fit (ensure_capacity)
@@ -187,6 +193,16 @@ inline hipError_t norm_adjoint(const df_train* t, int layer, float* zbar, int64_
     const float* xmn = t->c->d_params.as<const float>() + L.norm_off;
     return df::launch_norm_adjoint(zbar, xmn, xmn + P.d, L.alpha, L.beta, P.d, batch, st);
 }
+
+namespace df {
+namespace api {
+// df_train_logpdf_grad past its trainer-class and batch checks (df_train_capi.hip; batch > 0,
+// fused sweep).  flow: -1 θ as df_train_set_theta_input says, 1 raw θ normalised with the
+// chain's bounds, 0 θ as given.
+int score_sweep(df_train* t, const float* x, const float* theta, float* logpdf_out, float* grad_x, float* grad_theta,
+                int64_t batch, int flow, hipStream_t st);
+}  // namespace api
+}  // namespace df
 
 // df_lsweep.hip: the dynamic LDS its kernel families declare (df_train_create_opt), and the
 // reverse sweep of the layer-wise path (chain order, see df_ltrain.h).

@@ -13,9 +13,10 @@ from .chains import FlowChain, _n_of
 from .data import DataArrays, MetaData, maximum_theta, minimum_theta
 from .hip import as_julia_device, julia_empty
 
-__all__ = ["Flow", "MvNormal", "predict", "sample", "sample_with_rejection", "Box", "HalfSpaces", "Region",
-           "logpdf", "logpdf_grid", "logpdf_grad", "pdf", "pdf_marginals", "trapezoid_weights", "training_loss",
-           "validation_loss", "nll_partial_sum"]
+__all__ = ["Flow", "MvNormal", "predict", "sample", "sample_logpdf", "sample_with_rejection", "Box", "HalfSpaces",
+           "Region", "logpdf", "logpdf_grid", "logpdf_grad", "pdf", "pdf_marginals", "trapezoid_weights",
+           "training_loss", "validation_loss", "nll_partial_sum", "ScoreMoments", "score_moments",
+           "fisher_information", "entropy"]
 
 LOG2PI = float(np.log(2.0 * np.pi))
 
@@ -161,6 +162,57 @@ def sample(flow: Flow, dims: Union[int, Tuple[int, ...]], theta=None, rng=None, 
             thb, _, _ = as_julia_device(theta, flow.n, dev, "θ")
     h.run_sample(buf, thb, bcast, batch, seed, offset)
     return r
+
+
+def sample_logpdf(flow: Flow, dims: Union[int, Tuple[int, ...]], theta=None, rng=None, seed: Optional[int] = None,
+                  offset: int = 0):
+    """``(x, lp)``: a draw like :func:`sample`'s together with ``lp = log q(x | θ)`` of every
+    drawn point, shapes (d, dims...) and (dims...), from ONE forward pass per sample
+    (``df_flow_sample_logpdf``): the base log-density of the draw minus the forward ldj, where
+    ``sample`` then ``logpdf`` runs a forward and a full inverse pass.  Arguments as for
+    :func:`sample`.  ``x`` is ``forward`` of the ``(seed, offset)`` draw; ``sample`` runs
+    ``forward!`` on the same draw, and the two are not promised to agree bit for bit."""
+    import torch
+
+    from .hip import HIPChain
+
+    if isinstance(dims, int):
+        dims = (dims,)
+    dims = tuple(int(v) for v in dims)
+    bad = AssertionError("dimensions θ must match (n, dims...) with n number of trained parameters")
+    if flow.n > 0:
+        if theta is None or (isinstance(theta, tuple) and len(theta) != flow.n):
+            raise bad
+        if not isinstance(theta, tuple) and tuple(theta.shape) != (flow.n,) + dims:
+            raise bad
+    seed = _draw_seed(rng, seed)
+    h = flow.hip()
+    dev = h.device
+    buf, r = julia_empty(flow.d, dims, dev)
+    batch = int(np.prod(dims)) if dims else 1
+    lpb = torch.empty(batch, dtype=torch.float32, device=dev)
+    thb, bcast = None, False
+    if flow.n > 0:
+        if isinstance(theta, tuple):
+            thb, bcast = _theta_vector(theta, dev), True
+        else:
+            thb, _, _ = as_julia_device(theta, flow.n, dev, "θ")
+    h.run_sample_logpdf(buf, lpb, thb, bcast, batch, seed, offset)
+    return r, HIPChain._ldj_view(lpb, dims)
+
+
+def _draw_seed(rng, seed: Optional[int]) -> int:
+    """The 64-bit Philox key: ``seed``, or 64 bits drawn from ``rng`` as :func:`sample` draws them."""
+    if seed is not None:
+        return int(seed)
+    rng = rng if rng is not None else np.random.default_rng()
+    return int(rng.integers(0, 2**63 - 1, dtype=np.int64)) * 2 + int(rng.integers(0, 2))
+
+
+def _theta_vector(theta: tuple, dev):
+    import torch
+
+    return torch.tensor([float(np.float32(v)) for v in theta], dtype=torch.float32, device=dev)
 
 
 # ---------------------------------------------------------------------------
@@ -603,6 +655,151 @@ def logpdf_grad(flow: Flow, x, theta=None, state=None):
     if was_np:
         return _to_numpy(lpv), _to_numpy(gxv), _to_numpy(gtv)
     return lpv, gxv, gtv
+
+
+# ---------------------------------------------------------------------------
+# expectations under the flow, reduced on the device (df_moments.hip)
+# ---------------------------------------------------------------------------
+
+MAX_CHUNK = 1 << 24
+
+
+class ScoreMoments:
+    """The raw sums a moment reduction returns, as numpy float64: ``count``, ``lp_sum = Σ lp``,
+    ``lp_sqsum = Σ lp²``, ``score_sum = Σ g`` (n,) and ``outer = Σ g gᵀ`` (n, n), with
+    ``g = ∂lp/∂θ`` in the raw θ.  The properties are computed on the host in float64."""
+
+    def __init__(self, block, n: int):
+        block = np.asarray(block, dtype=np.float64).reshape(-1)
+        if block.shape[0] != 3 + n + n * n:
+            raise _lib.DimensionMismatch(f"a moment block for n = {n} has {3 + n + n * n} entries, got {block.shape[0]}")
+        self.n = int(n)
+        self.count = float(block[0])
+        self.lp_sum = float(block[1])
+        self.lp_sqsum = float(block[2])
+        self.score_sum = block[3:3 + n].copy()
+        self.outer = block[3 + n:].reshape(n, n, order="F").copy()
+
+    @property
+    def fisher(self) -> np.ndarray:
+        """``E[g gᵀ]`` (n, n): the Fisher matrix when the samples were drawn from the flow."""
+        return self.outer / self.count
+
+    @property
+    def mean_score(self) -> np.ndarray:
+        return self.score_sum / self.count
+
+    @property
+    def score_cov(self) -> np.ndarray:
+        m = self.mean_score
+        return self.fisher - np.outer(m, m)
+
+    @property
+    def entropy(self) -> float:
+        """``-E[lp]``: the entropy when the samples were drawn from the flow."""
+        return -self.lp_sum / self.count
+
+    @property
+    def entropy_stderr(self) -> float:
+        mean = self.lp_sum / self.count
+        return float(np.sqrt(max(0.0, self.lp_sqsum / self.count - mean * mean) / self.count))
+
+    def __repr__(self):
+        return f"ScoreMoments(n={self.n}, count={self.count:g})"
+
+
+def _check_draws(flow: Flow, theta, n_samples: int, chunk: int):
+    """The argument checks of :func:`fisher_information` and :func:`entropy`, before any library call."""
+    if not isinstance(theta, tuple) or len(theta) != flow.n:
+        raise _lib.DimensionMismatch(f"θ must be a tuple of the flow's n = {flow.n} conditions")
+    if int(n_samples) < 0:
+        raise _lib.DimensionMismatch("n_samples must be >= 0")
+    if int(chunk) < 0:
+        raise _lib.DimensionMismatch("chunk must be >= 0 (0: the library's default)")
+    if int(chunk) > MAX_CHUNK:
+        raise _lib.UnsupportedError("a chunk holds at most 2^24 samples")
+
+
+def _score_trainer(flow: Flow, state, who: str):
+    """(trainer, chain, temporary): ``state``'s trainer, or a temporary one on the flow's chain
+    holding the model's current parameters (as :func:`logpdf_grad` makes one)."""
+    from .train import Adam, HIPTrainer
+
+    if state is not None:
+        return state.trainer, state.trainer.chain, False
+    h = flow.hip()
+    try:
+        h.set_weights(flow.model.layers)
+    except _lib.ArgumentError as e:
+        raise _lib.ArgumentError(f"{who}: the flow has a live TrainState, pass it as state= ({e})") from e
+    return HIPTrainer(h, Adam()), h, True
+
+
+def _read_block(out, h):
+    import torch
+
+    torch.cuda.synchronize(h.device)
+    return out.cpu().numpy()
+
+
+def score_moments(flow: Flow, x, theta=None, state=None) -> ScoreMoments:
+    """The moments of :func:`logpdf_grad`'s ``lp`` and ``gθ`` over the points ``x`` (d, dims...),
+    reduced on the device (``df_train_score_moments``): only 3 + n + n² doubles reach the host.
+    θ (raw) and ``state`` as for :func:`logpdf_grad`."""
+    import torch
+
+    th = flow._theta(theta, x)
+    tr, h, temporary = _score_trainer(flow, state, "score_moments")
+    try:
+        xb, thb, dims, batch, _ = h._inputs(x, th, "x")
+        out = torch.empty(3 + h.n + h.n * h.n, dtype=torch.float64, device=h.device)
+        tr.score_moments(xb, thb, batch, out)
+        block = _read_block(out, h)
+    finally:
+        if temporary:
+            tr.close()
+    return ScoreMoments(block, h.n)
+
+
+def fisher_information(flow: Flow, theta: tuple, n_samples: int, chunk: int = 0, rng=None,
+                       seed: Optional[int] = None, offset: int = 0, state=None) -> ScoreMoments:
+    """The score moments over ``n_samples`` draws of the flow at the ONE raw condition ``theta``
+    (a tuple of n values), drawn, differentiated and reduced ``chunk`` samples at a time on the
+    device (``df_train_fisher``): ``.fisher`` is ``F(θ) = E_{x~q(x|θ)}[∂θ logq ∂θ logqᵀ]``,
+    ``.mean_score`` its Monte-Carlo check (it tends to 0), ``.entropy`` comes along.  Sample s
+    is sample s of ``sample(flow, n_samples, theta, seed=seed, offset=offset)``.  ``state`` as
+    for :func:`logpdf_grad`."""
+    import torch
+
+    _check_draws(flow, theta, n_samples, chunk)
+    seed = _draw_seed(rng, seed)
+    tr, h, temporary = _score_trainer(flow, state, "fisher_information")
+    try:
+        out = torch.empty(3 + h.n + h.n * h.n, dtype=torch.float64, device=h.device)
+        tr.fisher(_theta_vector(theta, h.device) if h.n > 0 else None, int(n_samples), out, int(chunk), seed,
+                  int(offset))
+        block = _read_block(out, h)
+    finally:
+        if temporary:
+            tr.close()
+    return ScoreMoments(block, h.n)
+
+
+def entropy(flow: Flow, n_samples: int, theta: tuple = (), chunk: int = 0, rng=None, seed: Optional[int] = None,
+            offset: int = 0) -> ScoreMoments:
+    """``{count, Σ lp, Σ lp²}`` of ``lp = log q(x | θ)`` over ``n_samples`` draws at the ONE raw
+    condition ``theta``, one forward pass per sample and no trainer
+    (``df_flow_sample_logpdf_moments``; every chain class): ``.entropy`` is ``H = -E[log q]``,
+    ``.entropy_stderr`` its standard error.  The score entries are empty (n = 0 in the result)."""
+    import torch
+
+    _check_draws(flow, theta, n_samples, chunk)
+    seed = _draw_seed(rng, seed)
+    h = flow.hip()
+    out = torch.empty(3, dtype=torch.float64, device=h.device)
+    h.run_sample_logpdf_moments(_theta_vector(theta, h.device) if h.n > 0 else None, int(n_samples), int(chunk),
+                                seed, int(offset), out)
+    return ScoreMoments(_read_block(out, h), 0)
 
 
 def pdf(flow: Flow, x, theta=None):

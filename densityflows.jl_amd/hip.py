@@ -312,6 +312,21 @@ class HIPChain:
                                            C.c_int64(batch), C.c_uint64(seed), C.c_uint64(offset),
                                            _stream(self.device)), "sample")
 
+    def run_sample_logpdf(self, xbuf, lpbuf, thbuf, broadcast: bool, batch: int, seed: int, offset: int = 0):
+        """df_flow_sample_logpdf: the draw sent through ``forward`` into ``xbuf`` and
+        ``log q(x | θ)`` of every drawn point into ``lpbuf`` (None: the draw and forward alone)."""
+        _lib.check(self.lib.df_flow_sample_logpdf(self.handle, _ptr(xbuf), _ptr(lpbuf), _ptr(thbuf),
+                                                  1 if broadcast else 0, C.c_int64(batch), C.c_uint64(seed),
+                                                  C.c_uint64(offset), _stream(self.device)), "sample_logpdf")
+
+    def run_sample_logpdf_moments(self, thvec, n_samples: int, chunk: int, seed: int, offset: int, outbuf):
+        """df_flow_sample_logpdf_moments: ``{count, Σ lp, Σ lp²}`` of ``n_samples`` draws at the
+        ONE raw θ ``thvec`` (device n-vector, None for n = 0) into the three float64 of ``outbuf``."""
+        _lib.check(self.lib.df_flow_sample_logpdf_moments(self.handle, _ptr(thvec), C.c_int64(n_samples),
+                                                          C.c_int64(chunk), C.c_uint64(seed), C.c_uint64(offset),
+                                                          _ptr(outbuf), _stream(self.device)),
+                   "sample_logpdf_moments")
+
     def run_sample_region(self, xbuf, thvec, n_want: int, lo, hi, A, b, max_tries: int, round: int, seed: int,
                           offset: int = 0):
         """df_flow_sample_region: the first ``n_want`` samples of the (seed, offset) candidate

@@ -229,6 +229,21 @@ class HIPTrainer:
         _lib.check(self.lib.df_train_logpdf_grad(self.handle, _ptr(xbuf), _ptr(thbuf), _ptr(lp), _ptr(gx), _ptr(gth),
                                                  C.c_int64(batch), _stream(self.device)), "df_train_logpdf_grad")
 
+    def score_moments(self, xbuf, thbuf, batch: int, out, accumulate: bool = False):
+        """df_train_score_moments on flat device buffers: the moment block of ``logpdf_grad``'s lp
+        and gθ over the batch into ``out`` (float64 device tensor of 3 + n + n²), overwritten or,
+        with ``accumulate``, added to."""
+        _lib.check(self.lib.df_train_score_moments(self.handle, _ptr(xbuf), _ptr(thbuf), C.c_int64(batch), _ptr(out),
+                                                   1 if accumulate else 0, _stream(self.device)),
+                   "df_train_score_moments")
+
+    def fisher(self, thvec, n_samples: int, out, chunk: int = 0, seed: int = 0, offset: int = 0):
+        """df_train_fisher: the moment block over ``n_samples`` draws at the ONE raw θ ``thvec``
+        (device n-vector, None for n = 0) into ``out`` (float64 device tensor of 3 + n + n²)."""
+        _lib.check(self.lib.df_train_fisher(self.handle, _ptr(thvec), C.c_int64(n_samples), C.c_int64(chunk),
+                                            C.c_uint64(seed), C.c_uint64(offset), _ptr(out), _stream(self.device)),
+                   "df_train_fisher")
+
     def grad(self):
         """The flat gradient as a torch tensor aliasing the device buffer."""
         import torch

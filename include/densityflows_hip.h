@@ -224,6 +224,55 @@ int df_flow_sample(df_chain* chain, float* x_out, const float* theta_raw, int th
                    uint64_t seed, uint64_t offset, void* stream);
 int df_random_normal(float* out, int64_t count, uint64_t seed, uint64_t offset, void* stream);
 
+/* ---- sampling with the density, and its moments (additive to ABI 5) -------------
+ * df_flow_sample_logpdf: x ~ q(. | θ) together with log q(x | θ), for importance weights,
+ * evidence estimates and entropies, at the cost of ONE forward pass per sample (sample then
+ * logpdf costs a forward and a full inverse pass).  Stream, θ handling (raw θ, bounds
+ * required when n > 0, theta_broadcast through the chain's θ workspace) and errors are
+ * df_flow_sample's.  With z the (d, batch) draw df_random_normal(seed, offset) returns:
+ *   x_out (d, batch)   bitwise what df_flow_forward(z, θ) returns.  df_flow_sample runs
+ *                      forward! instead; whether the two agree bit for bit is a property of
+ *                      the chain-pass kernels that nothing here promises.
+ *   logpdf_out[j]      = -(d·log(2π) + Σ_k z_kj²)/2 - ldj_j  with ldj bitwise
+ *                      df_flow_forward's, every operation one Float32 operation in this order:
+ *                        s = z_0j·z_0j;  s = s + z_kj·z_kj  for k = 1 .. d-1;
+ *                        b = -((float)d·(float)log(2π) + s) / 2;   logpdf_out[j] = b - ldj_j
+ * Three launches behind the draw: b into logpdf_out, df_flow_forward in place in x_out with
+ * the ldj into a workspace of max(batch, 1024) floats that belongs to the chain and only
+ * grows (growing it inside a stream capture is DF_ERR_INVALID), then the subtraction.  No
+ * host synchronisation; capturable once the workspaces are warm.
+ * logpdf_out == NULL: the draw and df_flow_forward alone.  batch == 0: DF_OK, nothing runs. */
+int df_flow_sample_logpdf(df_chain* chain, float* x_out, float* logpdf_out, const float* theta_raw,
+                          int theta_broadcast, int64_t batch, uint64_t seed, uint64_t offset, void* stream);
+/* The moment block of the calls below: 3 + m + m² doubles in DEVICE memory,
+ *   out[0]          = the number of samples, as a double
+ *   out[1], out[2]  = Σ_j lp_j,  Σ_j lp_j²
+ *   out[3 .. 3+m)   = Σ_j g_aj
+ *   out[3+m .. )    = Σ_j g_aj·g_bj, the full m × m matrix, column-major; both triangles
+ *                     hold the same bits
+ * of per-sample Float32 values lp_j and g_aj converted to double; products and sums are in
+ * double.  The sums are reduced WITHOUT atomics in a fixed order (two runs give the same
+ * bits): workgroup b of G sums a contiguous range of samples — thread i of 256 its samples
+ * i, i + 256, ... of the range in increasing order, the threads by a fixed tree — and the G
+ * partial blocks are then added in workgroup order.  G follows from the batch and the
+ * device (the chain's grid), so blocks of different batch sizes or devices differ in the
+ * last bits.  A non-finite value propagates into the entries it touches.  The partial
+ * blocks live in a workspace of the calling handle that only grows.
+ *
+ * df_flow_sample_logpdf_moments: m = 0, lp_j = log q(x_j | θ) of n_samples draws at ONE raw
+ * θ (a device n-vector; NULL for n = 0), every chain class: the entropy H = -out[1]/out[0]
+ * and its standard error from one forward pass per sample.  Sample s is sample s of
+ * df_flow_sample_logpdf(batch = n_samples, theta_broadcast = 1, seed, offset).  The call
+ * proceeds `chunk` samples at a time (0: 2^20; rounded up to a multiple of 4, a Philox
+ * counter boundary; at most 2^24): chunk i, starting at sample start_i, is
+ * df_flow_sample_logpdf at offset + d·start_i/4 into chain-owned workspaces (x, lp; they
+ * only grow, not inside a capture) and its block c_i is added to out3, which is zeroed on the
+ * stream first: out3 = ((0 + c_1) + c_2) + ...  No host synchronisation.
+ * n_samples == 0: DF_OK, out3 zeroed.  DF_ERR_INVALID: a null chain or out3, bounds not set
+ * (n > 0); DF_ERR_SHAPE: n_samples or chunk < 0, θ missing; DF_ERR_UNSUPPORTED: chunk > 2^24. */
+int df_flow_sample_logpdf_moments(df_chain* chain, const float* theta_raw, int64_t n_samples, int64_t chunk,
+                                  uint64_t seed, uint64_t offset, double* out3, void* stream);
+
 /* ---- grid logpdf ------------------------------------------------------------
  * logpdf(flow, (x_1, ..., x_d), (θ_1, ..., θ_n)) (src/Flows.jl:287-331; pdf, :348-349, is
  * its exp): the log-density on the outer product of one vector per dimension, generated on
@@ -448,6 +497,33 @@ int df_train_gradient(df_train* t, const float* x, const float* theta_raw, int64
  * trainer stays usable.  batch == 0: DF_OK, nothing written. */
 int df_train_logpdf_grad(df_train* t, const float* x, const float* theta, float* logpdf_out, float* grad_x,
                          float* grad_theta, int64_t batch, void* stream);
+/* Score moments (additive to ABI 5): df_train_logpdf_grad on (x, θ) reduced on the device into
+ * the moment block described at df_flow_sample_logpdf_moments, with m = n, lp = logpdf_out
+ * and g = grad_theta (n = 0: the three lp entries alone, the sweep is skipped).  Nothing of
+ * the batch's size reaches the host; lp, grad_theta and the sweep's z̄ go to workspaces the
+ * trainer owns (they only grow, not inside a stream capture).  θ is read as
+ * df_train_set_theta_input says, and the guarantee about the parameters, the optimiser
+ * state and the pending gradient is df_train_logpdf_grad's, as is DF_ERR_UNSUPPORTED for a
+ * layer-wise trainer (which stays usable).  accumulate == 0: out is overwritten;
+ * accumulate == 1: the block is added to out, one fp64 add per entry.  batch == 0: out is
+ * zeroed (accumulate == 0) or left as it is (accumulate == 1).  Correct for every n the
+ * chain limits allow, tuned for n <= 8 (one pass over the samples; a larger n takes one
+ * pass per pair of 8-row tiles of the matrix). */
+int df_train_score_moments(df_train* t, const float* x, const float* theta, int64_t batch, double* out,
+                           int accumulate, void* stream);
+/* The Fisher matrix F(θ) = E_{x ~ q(.|θ)}[∂θ logq ∂θ logqᵀ] = out[3+n ..] / out[0], with the
+ * mean score and the entropy sums beside it: the moment block over n_samples draws at ONE
+ * raw θ (a device n-vector, NULL for n = 0; bounds required as for df_flow_sample).  Sample s
+ * is sample s of df_flow_sample(batch = n_samples, seed, offset).  Chunks as for
+ * df_flow_sample_logpdf_moments; per chunk: df_flow_sample at offset + d·start_i/4 into a
+ * workspace, the score sweep in the RAW θ whatever df_train_set_theta_input says (the
+ * setting is left as it is), and the reduction added to out, which is zeroed on the stream
+ * first: out = ((0 + c_1) + c_2) + ...  No host synchronisation.  The workspaces (x, the θ
+ * broadcast, lp, gθ, z̄) belong to the trainer, only grow, and may not grow inside a capture.
+ * n_samples == 0: DF_OK, out zeroed.  Errors as df_flow_sample_logpdf_moments and
+ * df_train_score_moments. */
+int df_train_fisher(df_train* t, const float* theta_raw, int64_t n_samples, int64_t chunk, uint64_t seed,
+                    uint64_t offset, double* out, void* stream);
 /* Device pointer of the flat gradient (count floats); all-reduce it here
  * for multi-GPU data parallelism. */
 int df_train_grad_ptr(df_train* t, float** grad_dev);
