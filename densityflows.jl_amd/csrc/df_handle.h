@@ -148,6 +148,12 @@ struct df_chain {
     // lp (chunk), and the reduction's per-workgroup blocks (double [workgroups][3])
     DevBuf d_slp_ldj, d_mom_x, d_mom_lp, d_mom_part;
     int64_t slp_ldj_cap = 0, mom_x_cap = 0, mom_lp_cap = 0, mom_part_cap = 0;
+    // df_calib.hip; capacities in bytes, they only grow.  df_flow_hpd_ranks draws one chunk's x
+    // into d_mom_x, its base term into d_mom_lp and its ldj into d_slp_ldj; its own are the θ
+    // rows repeated over a chunk's draws (float [n · chunk]) and the points' lp (float
+    // [n_points], when the caller gives no logpdf_out)
+    DevBuf d_hpd_th, d_hpd_lp;
+    int64_t hpd_th_cap = 0, hpd_lp_cap = 0;
     ~df_chain() {
         if (d_theta_ws) (void)hipFree(d_theta_ws);
     }
@@ -203,6 +209,14 @@ int sample_check_theta(const df_chain* c, const float* theta_raw);
 // θ the pass reads.  batch > 0; the caller holds the device.
 int sample_draw(df_chain* c, float* x_out, const float* theta_raw, int theta_broadcast, int64_t batch, uint64_t seed,
                 uint64_t offset, void* stream, const float** theta_use);
+
+// df_moments.hip, shared with df_calib.hip.  capturing: the stream records a graph.  reserve: a
+// handle's workspace holds `need` bytes afterwards; it only grows, and not inside a capture.
+// launch_base_logpdf: the base term of df_flow_sample_logpdf (base_logpdf_kernel) of the (d, batch)
+// draw z into lp.
+bool capturing(hipStream_t st);
+int reserve(DevBuf& buf, int64_t& cap, int64_t need, hipStream_t st, const char* what);
+int launch_base_logpdf(const float* z, float* lp, int d, int64_t batch, hipStream_t st);
 
 // Launch one fused chain pass.  flow: θ normalised with the handle's bounds;
 // snap (inverse modes, specialised kernel): every layer's output kept.

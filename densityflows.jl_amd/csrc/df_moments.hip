@@ -177,6 +177,10 @@ int moments_grid(const df_chain* c, int64_t batch) {
     return (int)std::min<int64_t>((int64_t)std::max(1, c->grid_cus) * kMomWgPerCu, tiles);
 }
 
+}  // namespace
+
+namespace api {
+
 bool capturing(hipStream_t st) {
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cap) != hipSuccess) cap = hipStreamCaptureStatusNone;
@@ -199,6 +203,17 @@ int reserve(DevBuf& buf, int64_t& cap, int64_t need, hipStream_t st, const char*
     cap = need;
     return DF_OK;
 }
+
+int launch_base_logpdf(const float* z, float* lp, int d, int64_t batch, hipStream_t st) {
+    hipLaunchKernelGGL(base_logpdf_kernel, dim3(blocks256(batch)), dim3(256), 0, st, z, lp, d, batch,
+                       (float)d * (float)kLog2Pi);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? DF_OK : hip_err(e, "base logpdf kernel launch");
+}
+
+}  // namespace api
+
+namespace {
 
 // The reduction of (lp, g) over `batch` > 0 samples into out (3 + m + m² doubles), through
 // the caller's partial buffer (reserved for this batch).
@@ -251,16 +266,12 @@ static int sample_logpdf(df_chain* c, float* x_out, float* logpdf_out, const flo
     int rc = sample_draw(c, x_out, theta_raw, theta_broadcast, batch, seed, offset, stream, &th);
     if (rc != DF_OK) return rc;
     if (!logpdf_out) return df_flow_forward(c, x_out, th, x_out, nullptr, batch, stream);
-    const int d = c->plan.d;
-    hipLaunchKernelGGL(base_logpdf_kernel, dim3(blocks256(batch)), dim3(256), 0, st, x_out, logpdf_out, d, batch,
-                       (float)d * (float)kLog2Pi);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_err(e, "base logpdf kernel launch");
+    if ((rc = launch_base_logpdf(x_out, logpdf_out, c->plan.d, batch, st)) != DF_OK) return rc;
     float* ldj = c->d_slp_ldj.as<float>();
     rc = df_flow_forward(c, x_out, th, x_out, ldj, batch, stream);
     if (rc != DF_OK) return rc;
     hipLaunchKernelGGL(sub_ldj_kernel, dim3(blocks256(batch)), dim3(256), 0, st, logpdf_out, ldj, batch);
-    e = hipGetLastError();
+    const hipError_t e = hipGetLastError();
     return e == hipSuccess ? DF_OK : hip_err(e, "density combine kernel launch");
 }
 

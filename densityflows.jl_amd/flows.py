@@ -16,7 +16,7 @@ from .hip import as_julia_device, julia_empty
 __all__ = ["Flow", "MvNormal", "predict", "sample", "sample_logpdf", "sample_with_rejection", "Box", "HalfSpaces",
            "Region", "logpdf", "logpdf_grid", "logpdf_grad", "pdf", "pdf_marginals", "trapezoid_weights",
            "training_loss", "validation_loss", "nll_partial_sum", "ScoreMoments", "score_moments",
-           "fisher_information", "entropy"]
+           "fisher_information", "entropy", "hpd_levels", "expected_coverage"]
 
 LOG2PI = float(np.log(2.0 * np.pi))
 
@@ -800,6 +800,90 @@ def entropy(flow: Flow, n_samples: int, theta: tuple = (), chunk: int = 0, rng=N
     h.run_sample_logpdf_moments(_theta_vector(theta, h.device) if h.n > 0 else None, int(n_samples), int(chunk),
                                 seed, int(offset), out)
     return ScoreMoments(_read_block(out, h), 0)
+
+
+def hpd_levels(flow: Flow, x, theta=None, n_draws: int = 1024, chunk: int = 0, rng=None, seed: Optional[int] = None,
+               offset: int = 0, return_ranks: bool = False, return_logpdf: bool = False):
+    """The credibility levels of the expected-coverage (HPD rank) test, one library call
+    (``df_flow_hpd_ranks``; every chain class): for every point ``x[:, j]`` under its condition,
+    ``n_draws`` samples of ``q(. | θ_j)`` are drawn on the device and those with a higher density
+    than the point are counted there; the level is ``rank / n_draws``, uniform on [0, 1] for a
+    calibrated flow (:func:`expected_coverage`).
+
+    ``x`` is (d, dims...); ``theta`` an array (n, dims...) of raw θ or an NTuple used for every
+    point (broadcast on the device).  ``n_draws`` is a positive multiple of 4; ``chunk`` (in
+    samples, 0: 2²⁰, at most 2²⁴) bounds the workspace and does not change the result within
+    one chain-pass kernel family.  Draw k of point j is sample ``j·n_draws + k`` of
+    ``sample_logpdf`` at ``(seed, offset)`` with θ repeated per point.
+
+    Returns the float64 levels of shape ``dims`` (numpy); with ``return_ranks`` the int32 ranks
+    and with ``return_logpdf`` the points' float32 logpdf follow, in that order.  The count is
+    a Float32 ``>``: a point whose own logpdf is NaN (a non-finite or overflowing ``x``) counts
+    nothing and gets level 0; ask for the logpdf where the points may be non-finite."""
+    import torch
+
+    if len(x.shape) < 1 or int(x.shape[0]) != flow.d:
+        raise _lib.DimensionMismatch(f"x must have size ({flow.d}, dims...), got {tuple(x.shape)}")
+    dims = tuple(int(v) for v in x.shape[1:])
+    bad = AssertionError("dimensions θ must match (n, dims...) with n number of trained parameters")
+    if flow.n > 0:
+        if theta is None or (isinstance(theta, tuple) and len(theta) != flow.n):
+            raise bad
+        if not isinstance(theta, tuple) and tuple(theta.shape) != (flow.n,) + dims:
+            raise bad
+    n_draws = int(n_draws)
+    if n_draws <= 0 or n_draws % 4 != 0:
+        raise _lib.ArgumentError("n_draws must be a positive multiple of 4 (a Philox counter boundary)")
+    if n_draws > MAX_CHUNK:
+        raise _lib.UnsupportedError("a point has at most 2^24 draws (n_draws)")
+    if int(chunk) < 0:
+        raise _lib.DimensionMismatch("chunk must be >= 0 (0: the library's default)")
+    if int(chunk) > MAX_CHUNK:
+        raise _lib.UnsupportedError("a chunk holds at most 2^24 samples")
+    seed = _draw_seed(rng, seed)
+    h = flow.hip()
+    dev = h.device
+    xb, _, _ = as_julia_device(x, flow.d, dev, "x")
+    M = int(np.prod(dims)) if dims else 1
+    ranks = torch.empty(M, dtype=torch.int32, device=dev)
+    lpb = torch.empty(M, dtype=torch.float32, device=dev) if return_logpdf else None
+    with torch.cuda.device(dev):
+        thb = None
+        if flow.n > 0:
+            if isinstance(theta, tuple):
+                thb = torch.empty(flow.n * M, dtype=torch.float32, device=dev)
+                h.run_theta_broadcast(thb, _theta_vector(theta, dev), M)
+            else:
+                thb, _, _ = as_julia_device(theta, flow.n, dev, "θ")
+        if M > 0:
+            h.run_hpd_ranks(xb, thb, M, n_draws, int(chunk), seed, int(offset), ranks, lpb)
+        torch.cuda.synchronize(dev)
+    shape = lambda t: t.cpu().numpy().reshape(dims, order="F")
+    r = shape(ranks)
+    out = (r.astype(np.float64) / n_draws,)
+    if return_ranks:
+        out += (r,)
+    if return_logpdf:
+        out += (shape(lpb),)
+    return out if len(out) > 1 else out[0]
+
+
+def expected_coverage(levels, credibility=None):
+    """The expected-coverage curve of credibility levels (:func:`hpd_levels`), on the host:
+    ``(c, mean(levels <= c))`` for a grid of credibilities ``c`` (default
+    ``linspace(0, 1, 101)``).  A calibrated density gives the diagonal; a curve above it is
+    under-confident (too wide), below it over-confident.  Levels are multiples of
+    ``1 / n_draws``, so the curve is exact only to O(1 / n_draws).  NaN levels are refused."""
+    lv = np.asarray(levels, dtype=np.float64).ravel()
+    if np.any(np.isnan(lv)):
+        raise _lib.ArgumentError("expected_coverage: NaN levels")
+    c = np.linspace(0.0, 1.0, 101) if credibility is None else np.asarray(credibility, dtype=np.float64).ravel()
+    if np.any(np.isnan(c)):
+        raise _lib.ArgumentError("expected_coverage: NaN credibility")
+    if lv.size == 0:
+        raise _lib.ArgumentError("expected_coverage: no levels")
+    cov = np.searchsorted(np.sort(lv), c, side="right") / lv.size
+    return c, cov
 
 
 def pdf(flow: Flow, x, theta=None):

@@ -327,6 +327,18 @@ class HIPChain:
                                                           _ptr(outbuf), _stream(self.device)),
                    "sample_logpdf_moments")
 
+    def run_hpd_ranks(self, xbuf, thbuf, n_points: int, n_draws: int, chunk: int, seed: int, offset: int, rankbuf,
+                      lpbuf=None, drawsbuf=None):
+        """df_flow_hpd_ranks: for each of the ``n_points`` columns of ``xbuf`` (d, n_points) under
+        the raw θ columns of ``thbuf`` (n, n_points), the number of ``n_draws`` draws of the flow
+        at that θ whose density exceeds the point's, into the int32 ``rankbuf``.  ``lpbuf``
+        (n_points) takes the points' logpdf and ``drawsbuf`` (n_points · n_draws) the draws',
+        when given."""
+        _lib.check(self.lib.df_flow_hpd_ranks(self.handle, _ptr(xbuf), _ptr(thbuf), C.c_int64(n_points),
+                                              C.c_int64(n_draws), C.c_int64(chunk), C.c_uint64(seed),
+                                              C.c_uint64(offset), _ptr(rankbuf), _ptr(lpbuf), _ptr(drawsbuf),
+                                              _stream(self.device)), "hpd_ranks")
+
     def run_sample_region(self, xbuf, thvec, n_want: int, lo, hi, A, b, max_tries: int, round: int, seed: int,
                           offset: int = 0):
         """df_flow_sample_region: the first ``n_want`` samples of the (seed, offset) candidate

@@ -273,6 +273,42 @@ int df_flow_sample_logpdf(df_chain* chain, float* x_out, float* logpdf_out, cons
 int df_flow_sample_logpdf_moments(df_chain* chain, const float* theta_raw, int64_t n_samples, int64_t chunk,
                                   uint64_t seed, uint64_t offset, double* out3, void* stream);
 
+/* ---- calibration: HPD ranks of points under the flow (additive to ABI 5) ---------
+ * df_flow_hpd_ranks: the expected-coverage test of a conditional density, every chain class.
+ * For each of n_points held-out pairs (x_i, θ_i) the call draws n_draws samples of q(. | θ_i)
+ * and counts those with a higher density than x_i; rank_i / n_draws is the point's credibility
+ * level, uniform on [0, 1] for a calibrated flow.  All pointers are DEVICE memory.
+ *   x (d, n_points), theta_raw (n, n_points) raw θ (NULL for n = 0; bounds required as for
+ *   df_flow_sample).
+ *   rank_out[i]  (int32) = #{k < n_draws : lp_ik > lp_i}, a Float32 IEEE comparison: a NaN on
+ *                either side counts nothing; lp_i = -inf is below every finite draw.
+ *   lp_i         what df_flow_logpdf(x, theta_raw, batch = n_points) returns for point i (one
+ *                inverse pass over all points, before the first chunk); written to logpdf_out
+ *                when that is not NULL, otherwise to a workspace of the chain.
+ *   lp_ik        log q of draw k of point i; written to draws_logpdf_out[i·n_draws + k] when
+ *                that is not NULL (n_points · n_draws floats).
+ * Which draw is which: draw k of point i is sample j = i·n_draws + k of
+ * df_flow_sample_logpdf(batch = n_points·n_draws, theta_broadcast = 0, θ_j = θ_i, seed,
+ * offset), and lp_ik is bitwise that call's logpdf_out[j] wherever both run the same chain-pass
+ * kernel family: the same base term, the same df_flow_forward ldj and the same single Float32
+ * subtraction.  n_draws must be a positive multiple of 4 (a Philox counter boundary), so point
+ * i's draws start at counter offset + d·i·n_draws/4 and depend neither on the other points nor
+ * on the chunking.
+ * The call proceeds by whole points, G = max(1, chunk / n_draws) points at a time (chunk in
+ * samples; 0: 2^20; at most 2^24).  Per chunk: the draw, θ row i repeated over its draws, the
+ * base term, df_flow_forward in place with the ldj into a workspace, and one count kernel
+ * (wave64 ballots and population counts, the waves of a workgroup added through LDS in wave
+ * order, one store per point, no atomics).  The workspaces (x draws, repeated θ, base term,
+ * ldj, the points' lp) belong to the chain and only grow; growing one inside a stream capture
+ * is DF_ERR_INVALID.  No host synchronisation; capturable once the workspaces are warm.
+ * n_points == 0: DF_OK, nothing runs, nothing is written.
+ * DF_ERR_INVALID: a null chain, x or rank_out; n_draws not a positive multiple of 4; bounds
+ * not set (n > 0).  DF_ERR_SHAPE: n_points or chunk < 0, θ missing, n_points·n_draws past
+ * int64.  DF_ERR_UNSUPPORTED: chunk > 2^24, n_draws > 2^24. */
+int df_flow_hpd_ranks(df_chain* chain, const float* x, const float* theta_raw, int64_t n_points, int64_t n_draws,
+                      int64_t chunk, uint64_t seed, uint64_t offset, int32_t* rank_out, float* logpdf_out,
+                      float* draws_logpdf_out, void* stream);
+
 /* ---- grid logpdf ------------------------------------------------------------
  * logpdf(flow, (x_1, ..., x_d), (θ_1, ..., θ_n)) (src/Flows.jl:287-331; pdf, :348-349, is
  * its exp): the log-density on the outer product of one vector per dimension, generated on
