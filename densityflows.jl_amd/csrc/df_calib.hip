@@ -140,6 +140,18 @@ void launch_count(const float* base, const float* ldj, const float* lp_pts, int 
 }
 
 }  // namespace
+
+namespace api {
+
+int launch_theta_repeat(float* dst, const float* th, int n, int64_t n_draws, int64_t total, hipStream_t st) {
+    if ((total + 255) / 256 > 0x7fffffff) return set_err(DF_ERR_UNSUPPORTED, "chunk too large for one launch");
+    hipLaunchKernelGGL(theta_repeat_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, dst, th, n, n_draws,
+                       total);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? DF_OK : hip_err(e, "θ repeat kernel launch");
+}
+
+}  // namespace api
 }  // namespace df
 
 using namespace df;
@@ -200,13 +212,8 @@ int df_flow_hpd_ranks(df_chain* c, const float* x, const float* theta_raw, int64
         rc = sample_draw(c, xs, nullptr, 0, len, seed, offset + (uint64_t)((int64_t)d * p0 * L), stream, &unused);
         if (rc != DF_OK) return rc;
         hipError_t e;
-        if (n > 0) {
-            const int64_t total = (int64_t)n * len;
-            if ((total + 255) / 256 > 0x7fffffff) return set_err(DF_ERR_UNSUPPORTED, "chunk too large for one launch");
-            hipLaunchKernelGGL(theta_repeat_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, th,
-                               theta_raw + (int64_t)n * p0, n, n_draws, total);
-            if ((e = hipGetLastError()) != hipSuccess) return hip_err(e, "θ repeat kernel launch");
-        }
+        if (n > 0 && (rc = launch_theta_repeat(th, theta_raw + (int64_t)n * p0, n, n_draws, (int64_t)n * len, st)) != DF_OK)
+            return rc;
         if ((rc = launch_base_logpdf(xs, base, d, len, st)) != DF_OK) return rc;
         if ((rc = df_flow_forward(c, xs, th, xs, ldj, len, stream)) != DF_OK) return rc;
         if (draws_logpdf_out)

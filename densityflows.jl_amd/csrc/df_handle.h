@@ -152,6 +152,8 @@ struct df_chain {
     // into d_mom_x, its base term into d_mom_lp and its ldj into d_slp_ldj; its own are the θ
     // rows repeated over a chunk's draws (float [n · chunk]) and the points' lp (float
     // [n_points], when the caller gives no logpdf_out)
+    // df_pstats.hip: df_flow_point_stats draws one chunk's x into d_mom_x and repeats θ into
+    // d_hpd_th in the same way; it has no workspace of its own
     DevBuf d_hpd_th, d_hpd_lp;
     int64_t hpd_th_cap = 0, hpd_lp_cap = 0;
     ~df_chain() {
@@ -217,6 +219,10 @@ int sample_draw(df_chain* c, float* x_out, const float* theta_raw, int theta_bro
 bool capturing(hipStream_t st);
 int reserve(DevBuf& buf, int64_t& cap, int64_t need, hipStream_t st, const char* what);
 int launch_base_logpdf(const float* z, float* lp, int d, int64_t batch, hipStream_t st);
+
+// df_calib.hip, shared with df_pstats.hip.  theta_repeat_kernel: column i·n_draws + k of dst
+// (n, points · n_draws) is column i of th (n, points); total = n · points · n_draws > 0.
+int launch_theta_repeat(float* dst, const float* th, int n, int64_t n_draws, int64_t total, hipStream_t st);
 
 // Launch one fused chain pass.  flow: θ normalised with the handle's bounds;
 // snap (inverse modes, specialised kernel): every layer's output kept.

@@ -16,7 +16,8 @@ from .hip import as_julia_device, julia_empty
 __all__ = ["Flow", "MvNormal", "predict", "sample", "sample_logpdf", "sample_with_rejection", "Box", "HalfSpaces",
            "Region", "logpdf", "logpdf_grid", "logpdf_grad", "pdf", "pdf_marginals", "trapezoid_weights",
            "training_loss", "validation_loss", "nll_partial_sum", "ScoreMoments", "score_moments",
-           "fisher_information", "entropy", "hpd_levels", "expected_coverage"]
+           "fisher_information", "entropy", "hpd_levels", "expected_coverage", "PointStats", "posterior_stats",
+           "sbc_ranks", "sbc_histogram"]
 
 LOG2PI = float(np.log(2.0 * np.pi))
 
@@ -884,6 +885,167 @@ def expected_coverage(levels, credibility=None):
         raise _lib.ArgumentError("expected_coverage: no levels")
     cov = np.searchsorted(np.sort(lv), c, side="right") / lv.size
     return c, cov
+
+
+# ---------------------------------------------------------------------------
+# posterior summaries per condition, reduced on the device (df_pstats.hip)
+# ---------------------------------------------------------------------------
+
+class PointStats:
+    """What :func:`posterior_stats` returns, as numpy arrays in ``dims`` shape (``order="F"``):
+    ``mean`` (d, dims...) and ``cov`` (d, d, dims...) float64 of the ``n_draws`` draws of every
+    condition (the covariance with ``n_draws − 1`` in the denominator), ``std`` the square root
+    of its diagonal, and ``ranks`` (d, dims...) int32, the SBC ranks ``#{draw[k] < x[k]}`` when
+    points were given, else ``None``."""
+
+    def __init__(self, mean, cov, ranks, n_draws: int):
+        self.mean, self.cov, self.ranks, self.n_draws = mean, cov, ranks, int(n_draws)
+
+    @property
+    def std(self) -> np.ndarray:
+        d = self.mean.shape[0]
+        with np.errstate(invalid="ignore"):
+            return np.sqrt(self.cov[np.arange(d), np.arange(d)])
+
+    def zscore(self, x_true) -> np.ndarray:
+        """``(mean − x_true) / std`` per dimension and condition."""
+        x_true = np.asarray(x_true, dtype=np.float64)
+        if x_true.shape != self.mean.shape:
+            raise _lib.DimensionMismatch(f"x_true must have size {self.mean.shape}, got {x_true.shape}")
+        return (self.mean - x_true) / self.std
+
+    def __repr__(self):
+        return f"PointStats(d={self.mean.shape[0]}, dims={self.mean.shape[1:]}, n_draws={self.n_draws})"
+
+
+def moments_from_sums(block, d: int, n_draws: int):
+    """``(mean (d, M), cov (d, d, M))`` in float64 from the M blocks of ``df_flow_point_stats``'
+    ``sums_out`` — the shift ``c``, ``S1 = Σ (v − c)`` and the lower triangle of
+    ``S2 = Σ (v − c)(v − c)ᵀ``: ``mean = c + S1/N``, ``cov = (S2 − S1 S1ᵀ/N)/(N − 1)``."""
+    S = 2 * d + d * (d + 1) // 2
+    blk = np.asarray(block, dtype=np.float64).reshape(-1, S)
+    N = float(n_draws)
+    c, s1 = blk[:, :d], blk[:, d:2 * d]
+    a, b = np.tril_indices(d)                 # row-major lower triangle: index a(a+1)/2 + b
+    s2 = np.empty((blk.shape[0], d, d))
+    s2[:, a, b] = blk[:, 2 * d:]
+    s2[:, b, a] = blk[:, 2 * d:]
+    cov = (s2 - s1[:, :, None] * s1[:, None, :] / N) / (N - 1.0)
+    return (c + s1 / N).T, np.moveaxis(cov, 0, -1)
+
+
+def _check_point_draws(flow: Flow, x, theta, n_draws: int, chunk: int, dims):
+    """The argument checks of :func:`posterior_stats` and :func:`sbc_ranks` (those of
+    :func:`hpd_levels`), before any library call → ``dims``."""
+    if x is not None:
+        if len(x.shape) < 1 or int(x.shape[0]) != flow.d:
+            raise _lib.DimensionMismatch(f"x must have size ({flow.d}, dims...), got {tuple(x.shape)}")
+        xdims = tuple(int(v) for v in x.shape[1:])
+        if dims is not None and tuple(int(v) for v in dims) != xdims:
+            raise _lib.DimensionMismatch(f"dims = {tuple(dims)} does not match x of size {tuple(x.shape)}")
+        dims = xdims
+    bad = AssertionError("dimensions θ must match (n, dims...) with n number of trained parameters")
+    if flow.n > 0:
+        if theta is None or (isinstance(theta, tuple) and len(theta) != flow.n):
+            raise bad
+        if not isinstance(theta, tuple):
+            if len(theta.shape) < 1 or int(theta.shape[0]) != flow.n:
+                raise bad
+            tdims = tuple(int(v) for v in theta.shape[1:])
+            if dims is not None and tuple(int(v) for v in dims) != tdims:
+                raise bad
+            dims = tdims
+    if dims is None:
+        raise _lib.ArgumentError("an NTuple θ or an unconditional flow needs the points x or dims=")
+    dims = tuple(int(v) for v in dims)
+    n_draws = int(n_draws)
+    if n_draws <= 0 or n_draws % 4 != 0:
+        raise _lib.ArgumentError("n_draws must be a positive multiple of 4 (a Philox counter boundary)")
+    if n_draws > MAX_CHUNK:
+        raise _lib.UnsupportedError("a point has at most 2^24 draws (n_draws)")
+    if int(chunk) < 0:
+        raise _lib.DimensionMismatch("chunk must be >= 0 (0: the library's default)")
+    if int(chunk) > MAX_CHUNK:
+        raise _lib.UnsupportedError("a chunk holds at most 2^24 samples")
+    return dims
+
+
+def _point_stats(flow: Flow, x, theta, n_draws, chunk, rng, seed, offset, dims, want_sums: bool):
+    """One ``df_flow_point_stats`` call → (ranks (d, M) int32 or None, sums (M, S) or None, dims)."""
+    import torch
+
+    dims = _check_point_draws(flow, x, theta, n_draws, chunk, dims)
+    seed = _draw_seed(rng, seed)
+    h = flow.hip()
+    dev, d = h.device, flow.d
+    M = int(np.prod(dims)) if dims else 1
+    xb = as_julia_device(x, d, dev, "x")[0] if x is not None else None
+    ranks = torch.empty(d * M, dtype=torch.int32, device=dev) if x is not None else None
+    S = 2 * d + d * (d + 1) // 2
+    sums = torch.empty(M * S, dtype=torch.float64, device=dev) if want_sums else None
+    with torch.cuda.device(dev):
+        thb = None
+        if flow.n > 0:
+            if isinstance(theta, tuple):
+                thb = torch.empty(flow.n * M, dtype=torch.float32, device=dev)
+                h.run_theta_broadcast(thb, _theta_vector(theta, dev), M)
+            else:
+                thb, _, _ = as_julia_device(theta, flow.n, dev, "θ")
+        if M > 0:
+            h.run_point_stats(xb, thb, M, int(n_draws), int(chunk), seed, int(offset), ranks, sums)
+        torch.cuda.synchronize(dev)
+    r = ranks.cpu().numpy().reshape(M, d).T if ranks is not None else None
+    return r, (sums.cpu().numpy().reshape(M, S) if want_sums else None), dims
+
+
+def posterior_stats(flow: Flow, theta=None, n_draws: int = 1024, x=None, chunk: int = 0, rng=None,
+                    seed: Optional[int] = None, offset: int = 0, dims=None) -> PointStats:
+    """The mean and covariance of ``n_draws`` samples of ``q(. | θ_j)`` for every condition, one
+    library call (``df_flow_point_stats``; every chain class): the draws are made and reduced on
+    the device, ``d + d(d+1)/2`` fp64 sums and a shift per condition reach the host.  With the
+    points ``x`` (d, dims...) the SBC ranks of :func:`sbc_ranks` come along in ``.ranks``.
+
+    ``theta`` is an array (n, dims...) of raw θ, or an NTuple used for every point (broadcast on
+    the device), which then needs ``x`` or ``dims=`` for the shape; so does an unconditional
+    flow.  ``n_draws``, ``chunk``, ``seed``, ``offset`` as for :func:`hpd_levels`: draw k of
+    point j is sample ``j·n_draws + k`` of ``sample`` at ``(seed, offset)`` with θ repeated per
+    point, and its base normal is the one :func:`hpd_levels` uses at the same ``(seed, offset)``."""
+    r, blk, dims = _point_stats(flow, x, theta, n_draws, chunk, rng, seed, offset, dims, True)
+    d = flow.d
+    mean, cov = moments_from_sums(blk, d, int(n_draws))
+    return PointStats(np.asfortranarray(mean).reshape((d,) + dims, order="F"),
+                      np.asfortranarray(cov).reshape((d, d) + dims, order="F"),
+                      np.asfortranarray(r).reshape((d,) + dims, order="F") if r is not None else None, int(n_draws))
+
+
+def sbc_ranks(flow: Flow, x, theta=None, n_draws: int = 1024, chunk: int = 0, rng=None, seed: Optional[int] = None,
+              offset: int = 0) -> np.ndarray:
+    """The simulation-based-calibration ranks, one library call (``df_flow_point_stats``, its
+    ranks-only kernel): for every held-out pair ``(x[:, j], θ_j)`` and dimension k the number of
+    ``n_draws`` samples of ``q(. | θ_j)`` whose coordinate k lies below ``x[k, j]`` (a Float32
+    ``<``: a NaN coordinate gives rank 0), as int32 (d, dims...).  Uniform on ``{0 .. n_draws}``
+    for a calibrated flow (:func:`sbc_histogram`).  Arguments as for :func:`posterior_stats`."""
+    if x is None:
+        raise _lib.DimensionMismatch(f"x must have size ({flow.d}, dims...), got None")
+    r, _, dims = _point_stats(flow, x, theta, n_draws, chunk, rng, seed, offset, None, False)
+    return np.asfortranarray(r).reshape((flow.d,) + dims, order="F")
+
+
+def sbc_histogram(ranks, n_draws: int, bins: int) -> np.ndarray:
+    """The counts of SBC ranks (d, dims...) per dimension in ``bins`` equal groups of the
+    ``n_draws + 1`` possible values, on the host → int64 (d, bins); flat for a calibrated flow.
+    ``bins`` must divide ``n_draws + 1``."""
+    n_draws, bins = int(n_draws), int(bins)
+    if bins <= 0 or (n_draws + 1) % bins != 0:
+        raise _lib.ArgumentError(f"bins must divide n_draws + 1 = {n_draws + 1}")
+    r = np.asarray(ranks)
+    if r.ndim < 1 or not np.issubdtype(r.dtype, np.integer):
+        raise _lib.ArgumentError("ranks must be an integer array (d, dims...)")
+    r = r.reshape(r.shape[0], -1)
+    if r.size and (r.min() < 0 or r.max() > n_draws):
+        raise _lib.ArgumentError(f"ranks outside 0 .. n_draws = {n_draws}")
+    width = (n_draws + 1) // bins
+    return np.stack([np.bincount(row // width, minlength=bins) for row in r]).astype(np.int64).reshape(r.shape[0], bins)
 
 
 def pdf(flow: Flow, x, theta=None):

@@ -339,6 +339,19 @@ class HIPChain:
                                               C.c_uint64(offset), _ptr(rankbuf), _ptr(lpbuf), _ptr(drawsbuf),
                                               _stream(self.device)), "hpd_ranks")
 
+    def run_point_stats(self, xbuf, thbuf, n_points: int, n_draws: int, chunk: int, seed: int, offset: int,
+                        rankbuf=None, sumsbuf=None, drawsbuf=None):
+        """df_flow_point_stats: ``n_draws`` draws of the flow at each of the ``n_points`` raw θ
+        columns of ``thbuf`` (n, n_points), reduced per point.  ``rankbuf`` (int32, d · n_points;
+        needs the points ``xbuf`` (d, n_points)) takes the SBC ranks ``#{draw[k] < x[k]}``,
+        ``sumsbuf`` (float64, n_points blocks of 2d + d(d+1)/2) the shift, ``Σ (draw − c)`` and the
+        lower triangle of ``Σ (draw − c)(draw − c)ᵀ``, ``drawsbuf`` (d · n_points · n_draws) the
+        draws themselves; at least one of the three."""
+        _lib.check(self.lib.df_flow_point_stats(self.handle, _ptr(xbuf), _ptr(thbuf), C.c_int64(n_points),
+                                                C.c_int64(n_draws), C.c_int64(chunk), C.c_uint64(seed),
+                                                C.c_uint64(offset), _ptr(rankbuf), _ptr(sumsbuf), _ptr(drawsbuf),
+                                                _stream(self.device)), "point_stats")
+
     def run_sample_region(self, xbuf, thvec, n_want: int, lo, hi, A, b, max_tries: int, round: int, seed: int,
                           offset: int = 0):
         """df_flow_sample_region: the first ``n_want`` samples of the (seed, offset) candidate

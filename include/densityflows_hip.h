@@ -309,6 +309,53 @@ int df_flow_hpd_ranks(df_chain* chain, const float* x, const float* theta_raw, i
                       int64_t chunk, uint64_t seed, uint64_t offset, int32_t* rank_out, float* logpdf_out,
                       float* draws_logpdf_out, void* stream);
 
+/* ---- posterior summaries: SBC ranks, shifted sums per point (additive to ABI 5) ----
+ * df_flow_point_stats: the samples of q(. | θ_i) reduced per point, every chain class.  For each
+ * of n_points pairs (x_i, θ_i) the call draws n_draws samples and returns, per dimension k < d,
+ * the simulation-based-calibration rank of x_i[k] among them, and the sums behind the posterior
+ * mean and covariance.  All pointers are DEVICE memory, sample j at ptr + d·j.
+ *   x (d, n_points) the points, needed with rank_out only (NULL otherwise); theta_raw
+ *   (n, n_points) raw θ (NULL for n = 0; bounds required as for df_flow_sample).
+ *   rank_out[i·d + k] (int32) = #{j < n_draws : draw_ij[k] < x_i[k]}, a Float32 IEEE
+ *                comparison: a tie counts nothing, a NaN on either side counts nothing.
+ *                Uniform on {0 .. n_draws} for a calibrated flow.
+ *   sums_out     n_points blocks of S = 2d + d(d+1)/2 doubles.  Block i:
+ *                  c[k], k < d                 the shift: draw 0 of point i, as a double
+ *                  S1[k] at d + k              Σ_j (draw_ij[k] − c[k])
+ *                  S2[a, b] at 2d + a(a+1)/2 + b, a >= b
+ *                                              Σ_j (draw_ij[a] − c[a])·(draw_ij[b] − c[b])
+ *                every value converted to double before the subtraction; the products are
+ *                fused into the running sum (one rounding per term).  mean = c + S1/N,
+ *                cov = (S2 − S1 S1ᵀ/N)/(N − 1).  A NaN draw makes the sums it touches NaN, a
+ *                NaN in draw 0 every entry of its dimension; nothing is checked.
+ *   draws_out    (d, n_points·n_draws), when not NULL: the samples themselves, copied
+ *                device-to-device chunk by chunk; any 4-byte aligned pointer.
+ * At least one of the three outputs is given; the others may be NULL, and what is not asked for
+ * is not computed (ranks alone read no pair, sums alone read no point).
+ * Which draw is which: draw k of point i is sample j = i·n_draws + k of df_flow_sample(batch =
+ * n_points·n_draws, theta_broadcast = 0, θ_j = θ_i, seed, offset), bitwise wherever both run the
+ * same chain-pass kernel family, and its base normal is the one df_flow_hpd_ranks uses at the
+ * same (seed, offset).  n_draws must be a positive multiple of 4 (a Philox counter boundary):
+ * point i's draws start at counter offset + d·i·n_draws/4.
+ * The call proceeds by whole points, G = max(1, chunk / n_draws) points at a time (chunk in
+ * samples; 0: 2^20; at most 2^24).  Per chunk: the draw, θ row i repeated over its draws,
+ * df_flow_forward_inplace, and one reduction kernel.  The counts are exact.  Every fp64 sum is
+ * added in an order fixed by (d, n_draws) alone (tiles of 64 draws; df_pstats.hip states it),
+ * without atomics: two calls give the same bytes, whatever the chunk, the other points or the
+ * device's size, and so does point i computed alone at offset + d·i·n_draws/4 (within one
+ * chain-pass kernel family).
+ * The workspaces (x draws, repeated θ) are df_flow_hpd_ranks' own: they belong to the chain and
+ * only grow; growing one inside a stream capture is DF_ERR_INVALID.  No host synchronisation;
+ * capturable once the workspaces are warm.
+ * n_points == 0: DF_OK, nothing runs, nothing is written.
+ * DF_ERR_INVALID: a null chain; n_draws not a positive multiple of 4 (it is not rounded); all
+ * three outputs NULL; rank_out without x; bounds not set (n > 0).  DF_ERR_SHAPE: n_points or
+ * chunk < 0, θ missing, n_points·n_draws past int64.  DF_ERR_UNSUPPORTED: chunk > 2^24,
+ * n_draws > 2^24. */
+int df_flow_point_stats(df_chain* chain, const float* x, const float* theta_raw, int64_t n_points, int64_t n_draws,
+                        int64_t chunk, uint64_t seed, uint64_t offset, int32_t* rank_out, double* sums_out,
+                        float* draws_out, void* stream);
+
 /* ---- grid logpdf ------------------------------------------------------------
  * logpdf(flow, (x_1, ..., x_d), (θ_1, ..., θ_n)) (src/Flows.jl:287-331; pdf, :348-349, is
  * its exp): the log-density on the outer product of one vector per dimension, generated on
