@@ -13,10 +13,12 @@ from .axes import CouplingAxes, is_reverse, reverse
 from .chains import FlowChain, backward, concatenate, forward, forward_, forward_inplace
 from .data import (DataArrays, DataPartition, MetaData, dflt_theta, maximum_theta, minimum_theta,
                    normalize_input, resize_output)
-from .flows import (Box, Flow, HalfSpaces, MvNormal, PointStats, Region, ScoreMoments, entropy, expected_coverage,
-                    fisher_information, hpd_levels, logpdf, logpdf_grad, logpdf_grid, nll_partial_sum, pdf,
-                    pdf_marginals, posterior_stats, predict, sample, sample_logpdf, sample_with_rejection,
-                    sbc_histogram, sbc_ranks, score_moments, training_loss, trapezoid_weights, validation_loss)
+from .flows import (QUANT_MAX_ORDERS, Box, Flow, HalfSpaces, MvNormal, PointStats, Region, ScoreMoments,
+                    credible_intervals, entropy, expected_coverage, fisher_information, hpd_levels, logpdf,
+                    logpdf_grad, logpdf_grid, nll_partial_sum, order_statistics, pdf, pdf_marginals,
+                    posterior_quantiles, posterior_stats, predict, quantile_orders, sample, sample_logpdf,
+                    sample_with_rejection, sbc_histogram, sbc_ranks, score_moments, training_loss,
+                    trapezoid_weights, validation_loss)
 from .layers import (Chain, CouplingBlock, CouplingLayer, Dense, FlowElement, NICECouplingLayer,
                      NormalizationLayer, RNVPCouplingLayer, default_net)
 from .train import (Adam, AdamW, ClipGrad, ClipNorm, Descent, OptimiserChain, TrainState, WeightDecay, adjust_,

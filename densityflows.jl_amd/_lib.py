@@ -201,6 +201,9 @@ SIGNATURES = {
     "df_train_fisher": (C.c_int, [_VP, _VP, _I64, _I64, C.c_uint64, C.c_uint64, _VP, _VP]),
     "df_flow_hpd_ranks": (C.c_int, [_VP, _VP, _VP, _I64, _I64, _I64, C.c_uint64, C.c_uint64, _VP, _VP, _VP, _VP]),
     "df_flow_point_stats": (C.c_int, [_VP, _VP, _VP, _I64, _I64, _I64, C.c_uint64, C.c_uint64, _VP, _VP, _VP, _VP]),
+    "df_order_statistics": (C.c_int, [_VP, C.c_int, _I64, _I64, C.POINTER(C.c_int32), C.c_int, _VP, _VP]),
+    "df_flow_point_quantiles": (C.c_int, [_VP, _VP, _VP, _I64, _I64, _I64, C.c_uint64, C.c_uint64,
+                                          C.POINTER(C.c_int32), C.c_int, _VP, _VP, _VP, _VP, _VP]),
     "df_flow_sample_region": (C.c_int, [_VP, _VP, _VP, _I64, C.POINTER(df_region), _I64, _I64, C.c_uint64,
                                         C.c_uint64, C.POINTER(_I64), C.POINTER(_I64), _VP]),
     "df_flow_logpdf_grid": (C.c_int, [_VP, _VP, C.POINTER(_I64), _I64, _I64, _VP, _I64, _VP]),

@@ -224,6 +224,25 @@ int launch_base_logpdf(const float* z, float* lp, int d, int64_t batch, hipStrea
 // (n, points · n_draws) is column i of th (n, points); total = n · points · n_draws > 0.
 int launch_theta_repeat(float* dst, const float* th, int n, int64_t n_draws, int64_t total, hipStream_t st);
 
+// df_pstats.hip, shared with df_quant.hip.  point_check_sizes: the rules of df_flow_point_stats on
+// the chain pointer, n_points, n_draws and chunk, in its order and with its messages, before any
+// use of the handle.  point_draw_chunks: that call from its first use of the handle on — per
+// chunk of whole points the draw, the θ repeat, the forward pass, the copy into draws_out,
+// point_stats_kernel for rank_out / sums_out (each may be NULL), and, when quant_out is given,
+// the selection of the n_orders `orders` (HOST, checked by the caller) over the same chunk.
+// n_points > 0.
+int point_check_sizes(const df_chain* c, int64_t n_points, int64_t n_draws, int64_t chunk);
+int point_draw_chunks(df_chain* c, const float* x, const float* theta_raw, int64_t n_points, int64_t n_draws,
+                      int64_t chunk, uint64_t seed, uint64_t offset, int32_t* rank_out, double* sums_out,
+                      float* draws_out, const int32_t* orders, int n_orders, float* quant_out, void* stream);
+
+// df_quant.hip.  check_orders: orders non-null, 1 <= n_orders <= DF_QUANT_MAX_ORDERS, every order
+// in [0, n_draws).  launch_order_statistics: order_select_kernel over the (d, points · N) draws xs
+// (16-byte aligned, N a multiple of 4, points > 0, checked orders) into out[(i·d + k)·n_orders + q].
+int check_orders(const int32_t* orders, int n_orders, int64_t n_draws);
+int launch_order_statistics(const float* xs, int d, int N, int64_t points, const int32_t* orders, int n_orders,
+                            float* out, hipStream_t st);
+
 // Launch one fused chain pass.  flow: θ normalised with the handle's bounds;
 // snap (inverse modes, specialised kernel): every layer's output kept.
 int run(df_chain* c, int mode, bool flow, const float* zin, const float* theta, float* xout, float* ldj, float* lp,

@@ -3,6 +3,10 @@
 //                         n_draws samples of q(. | θ_i), one int32 per dimension, and the shifted
 //                         sums behind the posterior mean and covariance, 2d + d(d+1)/2 doubles
 //
+// The call's size rules and its chunk loop are point_check_sizes and point_draw_chunks, shared with
+// df_flow_point_quantiles (df_quant.hip) through df_handle.h: that call adds the selection of order
+// statistics at the end of every chunk; without orders the loop launches nothing else.
+//
 // Per chunk of whole points, as df_flow_hpd_ranks (df_calib.hip): the Philox draw, θ row i
 // repeated over the draws of point i, df_flow_forward_inplace (the pass df_flow_sample runs: no
 // ldj, no base term), and point_stats_kernel over the chunk's (d, points · N) array — d · N
@@ -346,11 +350,10 @@ hipError_t launch_stats(const float* xs, const float* x, int d, int N, int64_t p
 using namespace df;
 using namespace df::api;
 
-extern "C" {
+namespace df {
+namespace api {
 
-int df_flow_point_stats(df_chain* c, const float* x, const float* theta_raw, int64_t n_points, int64_t n_draws,
-                        int64_t chunk, uint64_t seed, uint64_t offset, int32_t* rank_out, double* sums_out,
-                        float* draws_out, void* stream) {
+int point_check_sizes(const df_chain* c, int64_t n_points, int64_t n_draws, int64_t chunk) {
     if (!c) return set_err(DF_ERR_INVALID, "null chain");
     if (n_points < 0) return set_err(DF_ERR_SHAPE, "negative point count");
     if (chunk < 0) return set_err(DF_ERR_SHAPE, "negative chunk size");
@@ -358,10 +361,12 @@ int df_flow_point_stats(df_chain* c, const float* x, const float* theta_raw, int
         return set_err(DF_ERR_INVALID, "n_draws must be a positive multiple of 4 (a Philox counter boundary)");
     if (chunk > kChunkMax) return set_err(DF_ERR_UNSUPPORTED, "a chunk holds at most 2^24 samples");
     if (n_draws > kDrawsMax) return set_err(DF_ERR_UNSUPPORTED, "a point has at most 2^24 draws (n_draws)");
-    if (!rank_out && !sums_out && !draws_out)
-        return set_err(DF_ERR_INVALID, "no output: rank_out, sums_out and draws_out are all null");
-    if (rank_out && !x) return set_err(DF_ERR_INVALID, "rank_out needs the points x (null input array)");
-    if (n_points == 0) return DF_OK;
+    return DF_OK;
+}
+
+int point_draw_chunks(df_chain* c, const float* x, const float* theta_raw, int64_t n_points, int64_t n_draws,
+                      int64_t chunk, uint64_t seed, uint64_t offset, int32_t* rank_out, double* sums_out,
+                      float* draws_out, const int32_t* orders, int n_orders, float* quant_out, void* stream) {
     // (the first use of the handle)
     int rc = sample_check_theta(c, theta_raw);
     if (rc != DF_OK) return rc;
@@ -412,8 +417,30 @@ int df_flow_point_stats(df_chain* c, const float* x, const float* theta_raw, int
         else if (sums_out)
             e = launch_stats<false, true>(xs, nullptr, d, N, pts, nullptr, sp, st);
         if (e != hipSuccess) return hip_err(e, "point statistics kernel launch");
+        // df_flow_point_quantiles: the selection reads the chunk the reduction has read
+        if (quant_out && (rc = launch_order_statistics(xs, d, N, pts, orders, n_orders,
+                                                       quant_out + (int64_t)d * p0 * n_orders, st)) != DF_OK)
+            return rc;
     }
     return DF_OK;
+}
+
+}  // namespace api
+}  // namespace df
+
+extern "C" {
+
+int df_flow_point_stats(df_chain* c, const float* x, const float* theta_raw, int64_t n_points, int64_t n_draws,
+                        int64_t chunk, uint64_t seed, uint64_t offset, int32_t* rank_out, double* sums_out,
+                        float* draws_out, void* stream) {
+    const int rc = point_check_sizes(c, n_points, n_draws, chunk);
+    if (rc != DF_OK) return rc;
+    if (!rank_out && !sums_out && !draws_out)
+        return set_err(DF_ERR_INVALID, "no output: rank_out, sums_out and draws_out are all null");
+    if (rank_out && !x) return set_err(DF_ERR_INVALID, "rank_out needs the points x (null input array)");
+    if (n_points == 0) return DF_OK;
+    return point_draw_chunks(c, x, theta_raw, n_points, n_draws, chunk, seed, offset, rank_out, sums_out, draws_out,
+                             nullptr, 0, nullptr, stream);
 }
 
 }  // extern "C"

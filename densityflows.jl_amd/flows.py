@@ -17,7 +17,8 @@ __all__ = ["Flow", "MvNormal", "predict", "sample", "sample_logpdf", "sample_wit
            "Region", "logpdf", "logpdf_grid", "logpdf_grad", "pdf", "pdf_marginals", "trapezoid_weights",
            "training_loss", "validation_loss", "nll_partial_sum", "ScoreMoments", "score_moments",
            "fisher_information", "entropy", "hpd_levels", "expected_coverage", "PointStats", "posterior_stats",
-           "sbc_ranks", "sbc_histogram"]
+           "sbc_ranks", "sbc_histogram", "QUANT_MAX_ORDERS", "quantile_orders", "order_statistics",
+           "posterior_quantiles", "credible_intervals"]
 
 LOG2PI = float(np.log(2.0 * np.pi))
 
@@ -1046,6 +1047,182 @@ def sbc_histogram(ranks, n_draws: int, bins: int) -> np.ndarray:
         raise _lib.ArgumentError(f"ranks outside 0 .. n_draws = {n_draws}")
     width = (n_draws + 1) // bins
     return np.stack([np.bincount(row // width, minlength=bins) for row in r]).astype(np.int64).reshape(r.shape[0], bins)
+
+
+# ---------------------------------------------------------------------------
+# posterior quantiles per condition and dimension, selected on the device (df_quant.hip)
+# ---------------------------------------------------------------------------
+
+QUANT_MAX_ORDERS = 32          # DF_QUANT_MAX_ORDERS
+
+
+def quantile_orders(probs, n_draws: int):
+    """The order statistics behind the quantiles ``probs`` of ``n_draws`` draws under the
+    ``linear`` (type 7) rule of numpy and of Julia's ``Statistics.quantile``: ``h = p·(N − 1)``,
+    ``j = floor(h)``, ``g = h − j``, quantile ``= v[j] + (v[min(j + 1, N − 1)] − v[j])·g`` of the
+    sorted draws ``v`` → ``(orders, lo_idx, hi_idx, frac)``: ``orders`` the sorted unique int32
+    set of every ``j`` and ``min(j + 1, N − 1)``, ``lo_idx`` / ``hi_idx`` the positions of the two
+    in ``orders`` and ``frac`` the float64 ``g``, one per probability.  No library call."""
+    p = np.atleast_1d(np.asarray(probs, dtype=np.float64)).reshape(-1)
+    N = int(n_draws)
+    if N <= 0:
+        raise _lib.ArgumentError("n_draws must be positive")
+    if p.size == 0:
+        raise _lib.ArgumentError("no probabilities")
+    if not np.all((p >= 0.0) & (p <= 1.0)):            # a NaN fails both comparisons
+        raise _lib.ArgumentError("probabilities must lie in [0, 1]")
+    h = p * (N - 1)
+    j = np.minimum(np.floor(h).astype(np.int64), N - 1)
+    frac = h - j
+    hi = np.minimum(j + 1, N - 1)
+    orders = np.unique(np.concatenate([j, hi]))
+    if orders.size > QUANT_MAX_ORDERS:
+        raise _lib.ArgumentError(f"{orders.size} order statistics needed, at most {QUANT_MAX_ORDERS} in one call")
+    return orders.astype(np.int32), np.searchsorted(orders, j), np.searchsorted(orders, hi), frac
+
+
+def _check_orders(orders, n_draws: int):
+    o = np.atleast_1d(np.asarray(orders))
+    if o.ndim != 1 or o.size == 0 or not np.issubdtype(o.dtype, np.integer):
+        raise _lib.ArgumentError("orders must be a non-empty vector of integers")
+    if o.size > QUANT_MAX_ORDERS:
+        raise _lib.UnsupportedError(f"at most {QUANT_MAX_ORDERS} orders in one call")
+    if o.min() < 0 or o.max() >= n_draws:
+        raise _lib.ArgumentError(f"orders must lie in [0, n_draws = {n_draws})")
+    return [int(v) for v in o]
+
+
+def order_statistics(draws, orders, device=None):
+    """The order statistics ``orders`` (0-based integers in ``[0, N)``, any order, repeats
+    allowed, at most 32) of every dimension of every point, selected on the device
+    (``df_order_statistics``) → float32 ``(M, d, Q)``, a numpy array for numpy draws and a
+    device tensor otherwise.  ``draws`` is a numpy ``(M, N, d)`` Float32 array or a device
+    tensor of that shape in C order (the layout of ``draws_out``: draw j of point i at
+    ``d·(i·N + j)``); ``N`` a multiple of 4, ``d <= 64``.  The order is IEEE totalOrder
+    (−NaN < −inf < ... < −0 < +0 < ... < +inf < +NaN); a result is one of the draws, bit for bit."""
+    import torch
+
+    from .hip import run_order_statistics
+
+    was_np = not isinstance(draws, torch.Tensor)
+    if was_np:
+        draws = np.asarray(draws)
+        if draws.dtype != np.float32:
+            raise _lib.ArgumentError(f"draws must be Float32 (got {draws.dtype})")
+    elif draws.dtype != torch.float32:
+        raise _lib.ArgumentError(f"draws must be Float32 (got {draws.dtype})")
+    if len(draws.shape) != 3:
+        raise _lib.DimensionMismatch(f"draws must have size (M, N, d), got {tuple(draws.shape)}")
+    M, N, d = (int(v) for v in draws.shape)
+    if not 1 <= d <= 64:
+        raise _lib.ArgumentError("d must be in 1 .. 64")
+    if N <= 0 or N % 4 != 0:
+        raise _lib.ArgumentError("n_draws must be a positive multiple of 4")
+    if N > MAX_CHUNK:
+        raise _lib.UnsupportedError("a point has at most 2^24 draws (n_draws)")
+    o = _check_orders(orders, N)
+    if was_np:
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        xs = torch.from_numpy(np.ascontiguousarray(draws)).to(dev)
+    else:
+        xs = draws.contiguous()
+        if xs.device.type != "cuda":
+            xs = xs.to(torch.device("cuda", torch.cuda.current_device()) if device is None else device)
+        if xs.data_ptr() % 16 != 0:
+            xs = xs.clone()
+    out = torch.empty((M, d, len(o)), dtype=torch.float32, device=xs.device)
+    if M > 0:
+        run_order_statistics(xs, d, M, N, o, out)
+    if was_np:
+        torch.cuda.synchronize(xs.device)
+        return out.cpu().numpy()
+    return out
+
+
+def _point_quantiles(flow: Flow, theta, probs, n_draws, x, chunk, rng, seed, offset, dims, want_sums, want_draws):
+    """One ``df_flow_point_quantiles`` call → (quantiles (P, d, M) float64, ranks (d, M) or None,
+    sums (M, S) or None, draws (M, N, d) float32 or None, dims)."""
+    import torch
+
+    dims = _check_point_draws(flow, x, theta, n_draws, chunk, dims)
+    N = int(n_draws)
+    orders, lo_i, hi_i, frac = quantile_orders(probs, N)
+    seed = _draw_seed(rng, seed)
+    h = flow.hip()
+    dev, d = h.device, flow.d
+    M = int(np.prod(dims)) if dims else 1
+    Q = int(orders.size)
+    xb = as_julia_device(x, d, dev, "x")[0] if x is not None else None
+    quant = torch.empty(M * d * Q, dtype=torch.float32, device=dev)
+    ranks = torch.empty(d * M, dtype=torch.int32, device=dev) if x is not None and want_sums else None
+    S = 2 * d + d * (d + 1) // 2
+    sums = torch.empty(M * S, dtype=torch.float64, device=dev) if want_sums else None
+    draws = torch.empty(M * N * d, dtype=torch.float32, device=dev) if want_draws else None
+    with torch.cuda.device(dev):
+        thb = None
+        if flow.n > 0:
+            if isinstance(theta, tuple):
+                thb = torch.empty(flow.n * M, dtype=torch.float32, device=dev)
+                h.run_theta_broadcast(thb, _theta_vector(theta, dev), M)
+            else:
+                thb, _, _ = as_julia_device(theta, flow.n, dev, "θ")
+        if M > 0:
+            h.run_point_quantiles(xb if ranks is not None else None, thb, M, N, int(chunk), seed, int(offset),
+                                  orders, quant, ranks, sums, draws)
+        torch.cuda.synchronize(dev)
+    v = quant.cpu().numpy().reshape(M, d, Q).astype(np.float64)
+    lo, hi = v[:, :, lo_i], v[:, :, hi_i]                     # (M, d, P)
+    with np.errstate(invalid="ignore"):
+        qv = lo + (hi - lo) * frac
+    qv = np.where((frac == 0.0) | (lo == hi), lo, qv)         # an order statistic itself, also when infinite
+    r = ranks.cpu().numpy().reshape(M, d).T if ranks is not None else None
+    return (np.ascontiguousarray(qv.transpose(2, 1, 0)), r, sums.cpu().numpy().reshape(M, S) if want_sums else None,
+            draws.cpu().numpy().reshape(M, N, d) if want_draws else None, dims)
+
+
+def posterior_quantiles(flow: Flow, theta=None, probs=(0.16, 0.5, 0.84), n_draws: int = 1024, x=None, chunk: int = 0,
+                        rng=None, seed: Optional[int] = None, offset: int = 0, return_stats: bool = False,
+                        dims=None, return_draws: bool = False):
+    """The quantiles ``probs`` of every dimension of ``n_draws`` samples of ``q(. | θ_j)`` for
+    every condition, one library call (``df_flow_point_quantiles``; every chain class): the draws
+    are made on the device, the order statistics that the quantiles need (:func:`quantile_orders`,
+    at most 32) are selected there exactly, and ``d · len(orders)`` floats per condition reach the
+    host → float64 ``(len(probs), d, dims...)``, ``lo + (hi − lo)·g`` of the two order statistics
+    in float64: ``np.quantile`` (``linear``) of the draws.
+
+    With ``return_stats=True`` the :class:`PointStats` of the same draws come along — the value
+    is ``(quantiles, stats)`` — with the SBC ranks when the points ``x`` are given; with
+    ``return_draws=True`` the draws themselves, numpy ``(M, n_draws, d)``, are appended.  The
+    other arguments, their checks and the draws are those of :func:`posterior_stats` at the same
+    ``(seed, offset)``."""
+    probs = np.atleast_1d(np.asarray(probs, dtype=np.float64))
+    qv, r, blk, draws, dims = _point_quantiles(flow, theta, probs, n_draws, x, chunk, rng, seed, offset, dims,
+                                               bool(return_stats), bool(return_draws))
+    d = flow.d
+    out = np.stack([np.asfortranarray(q).reshape((d,) + dims, order="F") for q in qv])
+    res = [out]
+    if return_stats:
+        mean, cov = moments_from_sums(blk, d, int(n_draws))
+        res.append(PointStats(np.asfortranarray(mean).reshape((d,) + dims, order="F"),
+                              np.asfortranarray(cov).reshape((d, d) + dims, order="F"),
+                              np.asfortranarray(r).reshape((d,) + dims, order="F") if r is not None else None,
+                              int(n_draws)))
+    if return_draws:
+        res.append(draws)
+    return res[0] if len(res) == 1 else tuple(res)
+
+
+def credible_intervals(flow: Flow, theta=None, level: float = 0.68, n_draws: int = 1024, x=None, chunk: int = 0,
+                       rng=None, seed: Optional[int] = None, offset: int = 0, dims=None):
+    """The equal-tailed credible interval of every dimension and condition →
+    ``(lower, median, upper)``, each float64 ``(d, dims...)``: :func:`posterior_quantiles` at
+    ``probs = ((1 − level)/2, 0.5, (1 + level)/2)``; ``0 < level < 1``."""
+    level = float(level)
+    if not 0.0 < level < 1.0:                                 # a NaN fails both comparisons
+        raise _lib.ArgumentError("level must lie in (0, 1)")
+    q = posterior_quantiles(flow, theta, ((1.0 - level) / 2, 0.5, (1.0 + level) / 2), n_draws, x, chunk, rng, seed,
+                            offset, False, dims)
+    return q[0], q[1], q[2]
 
 
 def pdf(flow: Flow, x, theta=None):

@@ -21,7 +21,7 @@ import numpy as np
 from . import _lib
 from .layers import (CouplingBlock, NICECouplingLayer, NormalizationLayer, RNVPCouplingLayer)
 
-__all__ = ["HIPChain", "flatten_elements", "as_julia_device", "julia_empty", "chain_dims"]
+__all__ = ["HIPChain", "flatten_elements", "as_julia_device", "julia_empty", "chain_dims", "run_order_statistics"]
 
 
 def _torch():
@@ -183,6 +183,28 @@ def validate(elements, n_hint: int | None = None):
     info = _lib.df_chain_info()
     _lib.check(lib.df_chain_validate(C.byref(desc.desc), C.byref(info)), "df_chain_validate")
     return info
+
+
+def _orders_array(orders):
+    """(ctypes int32 array or None, count) of host integers."""
+    if orders is None:
+        return None, 0
+    vals = [int(v) for v in orders]
+    return (C.c_int32 * max(len(vals), 1))(*vals), len(vals)
+
+
+def run_order_statistics(xs, d: int, n_points: int, n_draws: int, orders, out):
+    """df_order_statistics: the order statistics ``orders`` (host integers in ``[0, n_draws)``) of
+    every dimension of the ``n_points`` points of the device tensor ``xs`` (d, n_points · n_draws;
+    draw j of point i at ``d·(i·n_draws + j)``, 16-byte aligned) into the float32 device tensor
+    ``out``, element ``(i·d + k)·len(orders) + q``, on ``xs``' device and its current stream."""
+    import torch
+
+    arr, nq = _orders_array(orders)
+    lib = _lib.load()
+    with torch.cuda.device(xs.device):
+        _lib.check(lib.df_order_statistics(_ptr(xs), C.c_int(d), C.c_int64(n_points), C.c_int64(n_draws), arr,
+                                           C.c_int(nq), _ptr(out), _stream(xs.device)), "order_statistics")
 
 
 class HIPChain:
@@ -351,6 +373,25 @@ class HIPChain:
                                                 C.c_int64(n_draws), C.c_int64(chunk), C.c_uint64(seed),
                                                 C.c_uint64(offset), _ptr(rankbuf), _ptr(sumsbuf), _ptr(drawsbuf),
                                                 _stream(self.device)), "point_stats")
+
+    def run_point_quantiles(self, xbuf, thbuf, n_points: int, n_draws: int, chunk: int, seed: int, offset: int,
+                            orders, quantbuf=None, rankbuf=None, sumsbuf=None, drawsbuf=None):
+        """df_flow_point_quantiles: :meth:`run_point_stats` with the selection at the end of every
+        chunk.  ``quantbuf`` (float32, d · n_points · len(orders)) takes the order statistics
+        ``orders`` (host integers in ``[0, n_draws)``) of every dimension of every point, element
+        ``(i·d + k)·len(orders) + q``; ``rankbuf``, ``sumsbuf`` and ``drawsbuf`` as for
+        :meth:`run_point_stats`, of the same draws; at least one of the four."""
+        arr, nq = _orders_array(orders)
+        _lib.check(self.lib.df_flow_point_quantiles(self.handle, _ptr(xbuf), _ptr(thbuf), C.c_int64(n_points),
+                                                    C.c_int64(n_draws), C.c_int64(chunk), C.c_uint64(seed),
+                                                    C.c_uint64(offset), arr, C.c_int(nq), _ptr(quantbuf),
+                                                    _ptr(rankbuf), _ptr(sumsbuf), _ptr(drawsbuf),
+                                                    _stream(self.device)), "point_quantiles")
+
+    @staticmethod
+    def run_order_statistics(xs, d: int, n_points: int, n_draws: int, orders, out):
+        """df_order_statistics on device tensors: see :func:`run_order_statistics`."""
+        run_order_statistics(xs, d, n_points, n_draws, orders, out)
 
     def run_sample_region(self, xbuf, thvec, n_want: int, lo, hi, A, b, max_tries: int, round: int, seed: int,
                           offset: int = 0):

@@ -356,7 +356,54 @@ int df_flow_point_stats(df_chain* chain, const float* x, const float* theta_raw,
                         int64_t chunk, uint64_t seed, uint64_t offset, int32_t* rank_out, double* sums_out,
                         float* draws_out, void* stream);
 
-/* ---- grid logpdf ------------------------------------------------------------
+/* ---- posterior quantiles: order statistics per point and dimension (additive to ABI 5) ----
+ * The order on Float32 is IEEE totalOrder: key = bits ^ (bits >> 31 ? 0xFFFFFFFF : 0x80000000),
+ * compared as uint32: −NaN < −inf < ... < −0 < +0 < ... < +inf < +NaN.  The order statistic r
+ * (0-based, 0 <= r < n_draws) of dimension k of a point is the draw whose key is the r-th
+ * smallest among the point's n_draws draws of that dimension, returned with its own bits; ties
+ * hold equal keys and hence equal bits.  Nothing is interpolated on the device: a quantile
+ * between two draws is the caller's lo + (hi − lo)·g from two order statistics.
+ *
+ * df_order_statistics: the selection alone, on the current device (as df_random_normal).
+ *   xs (d, n_points·n_draws) DEVICE, 16-byte aligned, draw j of point i at xs + d·(i·n_draws + j);
+ *   orders: HOST array of n_orders int32, each in [0, n_draws), in any order, repeats allowed;
+ *           read at call time and passed to the kernel by value: no copy, no synchronisation,
+ *           capturable;
+ *   out[(i·d + k)·n_orders + q] (DEVICE) = order statistic orders[q] of dimension k of point i.
+ * One radix-select kernel (df_quant.hip: 8-bit digits, 4 passes over a point's draws, integer
+ * counts in LDS, a wave per point up to n_draws = 256 and a workgroup per point above; what does
+ * not fit the LDS at once is walked in groups of dimensions).  One store per (point, dimension,
+ * order); nothing is zeroed, no global atomics: two calls give the same bytes.
+ * Checked in this order before any device work: 1 <= d <= 64 (DF_ERR_INVALID); n_points < 0
+ * (DF_ERR_SHAPE); n_draws a positive multiple of 4 (DF_ERR_INVALID) and at most 2^24
+ * (DF_ERR_UNSUPPORTED); xs and out non-null, xs 16-byte aligned (DF_ERR_INVALID); orders
+ * non-null (DF_ERR_INVALID), 1 <= n_orders <= DF_QUANT_MAX_ORDERS (DF_ERR_UNSUPPORTED), every
+ * order in [0, n_draws) (DF_ERR_INVALID, the message names the index).  Then n_points == 0:
+ * DF_OK, nothing launched, nothing written.
+ *
+ * df_flow_point_quantiles: df_flow_point_stats with the selection at the end of every chunk.
+ * The draws, the θ repeat, the chunking by whole points, the workspaces, the counters
+ * (offset + d·i·n_draws/4) and the rules and messages for the chain, n_points, n_draws, chunk,
+ * θ and the bounds are df_flow_point_stats': draw j of point i is bitwise the draw that call
+ * makes at the same (seed, offset).  quant_out is as `out` above.  rank_out (needs x), sums_out
+ * and draws_out are optional and bitwise what df_flow_point_stats writes (the same kernel and
+ * the same copy, on the chunk the selection reads).  At least one of the four outputs is given;
+ * quant_out needs orders and 1 <= n_orders <= DF_QUANT_MAX_ORDERS, checked as above after the
+ * outputs; with quant_out NULL, orders and n_orders are ignored.  The workspaces are
+ * df_flow_hpd_ranks' and df_flow_point_stats': calls on different streams must not overlap.
+ * No host synchronisation; capturable once the workspaces are warm.  n_points == 0: DF_OK,
+ * nothing runs, nothing is written (the argument rules still hold). */
+#define DF_QUANT_MAX_ORDERS 32
+
+int df_order_statistics(const float* xs, int d, int64_t n_points, int64_t n_draws, const int32_t* orders,
+                        int n_orders, float* out, void* stream);
+
+int df_flow_point_quantiles(df_chain* chain, const float* x, const float* theta_raw, int64_t n_points,
+                            int64_t n_draws, int64_t chunk, uint64_t seed, uint64_t offset, const int32_t* orders,
+                            int n_orders, float* quant_out, int32_t* rank_out, double* sums_out, float* draws_out,
+                            void* stream);
+
+/* ---- grid logpdf------------------------------------------------------------
  * logpdf(flow, (x_1, ..., x_d), (θ_1, ..., θ_n)) (src/Flows.jl:287-331; pdf, :348-349, is
  * its exp): the log-density on the outer product of one vector per dimension, generated on
  * the device — nothing of the grid's size is built on the host.
