@@ -13,10 +13,12 @@ from .axes import CouplingAxes, is_reverse, reverse
 from .chains import FlowChain, backward, concatenate, forward, forward_, forward_inplace
 from .data import (DataArrays, DataPartition, MetaData, dflt_theta, maximum_theta, minimum_theta,
                    normalize_input, resize_output)
-from .flows import (QUANT_MAX_ORDERS, Box, Flow, HalfSpaces, MvNormal, PointStats, Region, ScoreMoments,
-                    credible_intervals, entropy, expected_coverage, fisher_information, hpd_levels, logpdf,
+from .flows import (HIST_MAX_BINS, HIST_MAX_TABLES, HIST_SPLIT_DRAWS, QUANT_MAX_ORDERS, Box, Flow, HalfSpaces,
+                    MvNormal, PointHistograms, PointStats, Region, ScoreMoments, credible_intervals,
+                    draw_histograms, entropy, expected_coverage, fisher_information, histogram_edges, hpd_levels,
+                    logpdf,
                     logpdf_grad, logpdf_grid, nll_partial_sum, order_statistics, pdf, pdf_marginals,
-                    posterior_quantiles, posterior_stats, predict, quantile_orders, sample, sample_logpdf,
+                    posterior_histograms, posterior_quantiles, posterior_stats, predict, quantile_orders, sample, sample_logpdf,
                     sample_with_rejection, sbc_histogram, sbc_ranks, score_moments, training_loss,
                     trapezoid_weights, validation_loss)
 from .layers import (Chain, CouplingBlock, CouplingLayer, Dense, FlowElement, NICECouplingLayer,

@@ -224,17 +224,42 @@ int launch_base_logpdf(const float* z, float* lp, int d, int64_t batch, hipStrea
 // (n, points · n_draws) is column i of th (n, points); total = n · points · n_draws > 0.
 int launch_theta_repeat(float* dst, const float* th, int n, int64_t n_draws, int64_t total, hipStream_t st);
 
-// df_pstats.hip, shared with df_quant.hip.  point_check_sizes: the rules of df_flow_point_stats on
-// the chain pointer, n_points, n_draws and chunk, in its order and with its messages, before any
-// use of the handle.  point_draw_chunks: that call from its first use of the handle on — per
-// chunk of whole points the draw, the θ repeat, the forward pass, the copy into draws_out,
-// point_stats_kernel for rank_out / sums_out (each may be NULL), and, when quant_out is given,
-// the selection of the n_orders `orders` (HOST, checked by the caller) over the same chunk.
-// n_points > 0.
+// df_pstats.hip, shared with df_quant.hip and df_hist.hip.  point_check_sizes: the rules of
+// df_flow_point_stats on the chain pointer, n_points, n_draws and chunk, in its order and with
+// its messages, before any use of the handle.  point_draw_chunks: that call from its first use of
+// the handle on — per chunk of whole points the draw, the θ repeat, the forward pass, and what
+// `out` asks for over the chunk, every member optional: the copy into draws, point_stats_kernel
+// for rank (needs x) / sums, the selection of the n_orders `orders` (HOST, checked by the
+// caller) into quant, and the tables of the planned histograms `hist` (edges: DEVICE) into
+// counts.  n_points > 0.
+struct HistTables;
+struct PointOutputs {
+    int32_t* rank = nullptr;
+    double* sums = nullptr;
+    float* draws = nullptr;
+    const int32_t* orders = nullptr;
+    int n_orders = 0;
+    float* quant = nullptr;
+    const HistTables* hist = nullptr;
+    const float* edges = nullptr;
+    int32_t* counts = nullptr;
+};
 int point_check_sizes(const df_chain* c, int64_t n_points, int64_t n_draws, int64_t chunk);
 int point_draw_chunks(df_chain* c, const float* x, const float* theta_raw, int64_t n_points, int64_t n_draws,
-                      int64_t chunk, uint64_t seed, uint64_t offset, int32_t* rank_out, double* sums_out,
-                      float* draws_out, const int32_t* orders, int n_orders, float* quant_out, void* stream);
+                      int64_t chunk, uint64_t seed, uint64_t offset, const PointOutputs& out, void* stream);
+
+// df_hist.hip.  check_histogram_tables: rules 4 (edges, bins, keep non-null) to 8 of
+// df_draw_histograms; with a chain, d is the chain's, read after the n_tables rule.
+// plan_histograms: the groups of checked tables for both team sizes (free_histograms).
+// launch_draw_histograms: draw_hist_kernel over the (d, points · N) draws xs (16-byte aligned, N a
+// multiple of 4, points > 0) into the points' blocks at counts, zeroed first on the split path.
+int check_histogram_tables(const df_chain* c, int d, const float* edges, const int32_t* bins, const int32_t* keep,
+                           int32_t n_tables, int64_t n_points, int64_t* block_words);
+HistTables* plan_histograms(int d, const int32_t* bins, const int32_t* keep, int32_t n_tables);
+void free_histograms(HistTables* h);
+int64_t histogram_block_words(const HistTables* h);
+int launch_draw_histograms(const float* xs, int d, int N, int64_t points, const float* edges, const HistTables* h,
+                           int32_t* counts, hipStream_t st);
 
 // df_quant.hip.  check_orders: orders non-null, 1 <= n_orders <= DF_QUANT_MAX_ORDERS, every order
 // in [0, n_draws).  launch_order_statistics: order_select_kernel over the (d, points · N) draws xs

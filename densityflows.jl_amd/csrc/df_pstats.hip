@@ -4,8 +4,9 @@
 //                         sums behind the posterior mean and covariance, 2d + d(d+1)/2 doubles
 //
 // The call's size rules and its chunk loop are point_check_sizes and point_draw_chunks, shared with
-// df_flow_point_quantiles (df_quant.hip) through df_handle.h: that call adds the selection of order
-// statistics at the end of every chunk; without orders the loop launches nothing else.
+// df_flow_point_quantiles (df_quant.hip) and df_flow_point_histograms (df_hist.hip) through
+// df_handle.h: those calls add the selection of order statistics, or the counting of the marginal
+// tables, at the end of every chunk; what PointOutputs does not ask for is not launched.
 //
 // Per chunk of whole points, as df_flow_hpd_ranks (df_calib.hip): the Philox draw, θ row i
 // repeated over the draws of point i, df_flow_forward_inplace (the pass df_flow_sample runs: no
@@ -365,8 +366,11 @@ int point_check_sizes(const df_chain* c, int64_t n_points, int64_t n_draws, int6
 }
 
 int point_draw_chunks(df_chain* c, const float* x, const float* theta_raw, int64_t n_points, int64_t n_draws,
-                      int64_t chunk, uint64_t seed, uint64_t offset, int32_t* rank_out, double* sums_out,
-                      float* draws_out, const int32_t* orders, int n_orders, float* quant_out, void* stream) {
+                      int64_t chunk, uint64_t seed, uint64_t offset, const PointOutputs& out, void* stream) {
+    int32_t* const rank_out = out.rank;
+    double* const sums_out = out.sums;
+    float* const draws_out = out.draws;
+    float* const quant_out = out.quant;
     // (the first use of the handle)
     int rc = sample_check_theta(c, theta_raw);
     if (rc != DF_OK) return rc;
@@ -418,8 +422,12 @@ int point_draw_chunks(df_chain* c, const float* x, const float* theta_raw, int64
             e = launch_stats<false, true>(xs, nullptr, d, N, pts, nullptr, sp, st);
         if (e != hipSuccess) return hip_err(e, "point statistics kernel launch");
         // df_flow_point_quantiles: the selection reads the chunk the reduction has read
-        if (quant_out && (rc = launch_order_statistics(xs, d, N, pts, orders, n_orders,
-                                                       quant_out + (int64_t)d * p0 * n_orders, st)) != DF_OK)
+        if (quant_out && (rc = launch_order_statistics(xs, d, N, pts, out.orders, out.n_orders,
+                                                       quant_out + (int64_t)d * p0 * out.n_orders, st)) != DF_OK)
+            return rc;
+        // df_flow_point_histograms: the tables of the chunk's points
+        if (out.counts && (rc = launch_draw_histograms(xs, d, N, pts, out.edges, out.hist,
+                                                       out.counts + histogram_block_words(out.hist) * p0, st)) != DF_OK)
             return rc;
     }
     return DF_OK;
@@ -439,8 +447,11 @@ int df_flow_point_stats(df_chain* c, const float* x, const float* theta_raw, int
         return set_err(DF_ERR_INVALID, "no output: rank_out, sums_out and draws_out are all null");
     if (rank_out && !x) return set_err(DF_ERR_INVALID, "rank_out needs the points x (null input array)");
     if (n_points == 0) return DF_OK;
-    return point_draw_chunks(c, x, theta_raw, n_points, n_draws, chunk, seed, offset, rank_out, sums_out, draws_out,
-                             nullptr, 0, nullptr, stream);
+    PointOutputs out;
+    out.rank = rank_out;
+    out.sums = sums_out;
+    out.draws = draws_out;
+    return point_draw_chunks(c, x, theta_raw, n_points, n_draws, chunk, seed, offset, out, stream);
 }
 
 }  // extern "C"

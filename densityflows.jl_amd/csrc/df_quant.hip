@@ -288,8 +288,16 @@ int df_flow_point_quantiles(df_chain* c, const float* x, const float* theta_raw,
     if (rank_out && !x) return set_err(DF_ERR_INVALID, "rank_out needs the points x (null input array)");
     if (quant_out && (rc = check_orders(orders, n_orders, n_draws)) != DF_OK) return rc;
     if (n_points == 0) return DF_OK;
-    return point_draw_chunks(c, x, theta_raw, n_points, n_draws, chunk, seed, offset, rank_out, sums_out, draws_out,
-                             quant_out ? orders : nullptr, quant_out ? n_orders : 0, quant_out, stream);
+    PointOutputs out;
+    out.rank = rank_out;
+    out.sums = sums_out;
+    out.draws = draws_out;
+    if (quant_out) {
+        out.orders = orders;
+        out.n_orders = n_orders;
+        out.quant = quant_out;
+    }
+    return point_draw_chunks(c, x, theta_raw, n_points, n_draws, chunk, seed, offset, out, stream);
 }
 
 }  // extern "C"

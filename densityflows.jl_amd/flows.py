@@ -18,7 +18,8 @@ __all__ = ["Flow", "MvNormal", "predict", "sample", "sample_logpdf", "sample_wit
            "training_loss", "validation_loss", "nll_partial_sum", "ScoreMoments", "score_moments",
            "fisher_information", "entropy", "hpd_levels", "expected_coverage", "PointStats", "posterior_stats",
            "sbc_ranks", "sbc_histogram", "QUANT_MAX_ORDERS", "quantile_orders", "order_statistics",
-           "posterior_quantiles", "credible_intervals"]
+           "posterior_quantiles", "credible_intervals", "HIST_MAX_BINS", "HIST_MAX_TABLES", "HIST_SPLIT_DRAWS",
+           "histogram_edges", "draw_histograms", "posterior_histograms", "PointHistograms"]
 
 LOG2PI = float(np.log(2.0 * np.pi))
 
@@ -1223,6 +1224,230 @@ def credible_intervals(flow: Flow, theta=None, level: float = 0.68, n_draws: int
     q = posterior_quantiles(flow, theta, ((1.0 - level) / 2, 0.5, (1.0 + level) / 2), n_draws, x, chunk, rng, seed,
                             offset, False, dims)
     return q[0], q[1], q[2]
+
+
+# ---------------------------------------------------------------------------
+# posterior histograms per condition: 1-D and 2-D marginal counts on the device (df_hist.hip)
+# ---------------------------------------------------------------------------
+
+HIST_MAX_BINS = 128            # DF_HIST_MAX_BINS
+HIST_MAX_TABLES = 2080         # DF_HIST_MAX_TABLES
+HIST_SPLIT_DRAWS = 2048        # DF_HIST_SPLIT_DRAWS
+
+
+def histogram_edges(spec, d: int):
+    """The per-dimension bin edges of the histogram calls → ``(edges, bins)``: ``edges`` a list of
+    d Float32 vectors (``None`` for a dimension without bins) and ``bins`` the d int32 bin counts
+    (0 there).  ``spec`` holds one entry per dimension: ``None``, a 1-D increasing array of 2 to
+    129 edges, or a tuple ``(lo, hi, nbins)`` with an integer ``nbins`` — ``np.linspace(lo, hi,
+    nbins + 1)`` in float64, rounded to Float32.  Edges must be free of NaN and strictly
+    increasing as Float32 (infinite outer edges are allowed).  No library call."""
+    d = int(d)
+    spec = list(spec)
+    if len(spec) != d:
+        raise _lib.DimensionMismatch(f"edges must hold d = {d} entries (None, an array or (lo, hi, nbins)), got {len(spec)}")
+    edges, bins = [], np.zeros(d, np.int32)
+    for k, e in enumerate(spec):
+        if e is None:
+            edges.append(None)
+            continue
+        if isinstance(e, tuple) and len(e) == 3 and isinstance(e[2], (int, np.integer)) and not isinstance(e[2], bool):
+            lo, hi, nb = float(e[0]), float(e[1]), int(e[2])
+            if nb < 1 or nb > HIST_MAX_BINS:
+                raise _lib.ArgumentError(f"edges of dimension {k}: nbins = {nb} is outside 1 .. {HIST_MAX_BINS}")
+            e = np.linspace(lo, hi, nb + 1, dtype=np.float64)
+        if hasattr(e, "detach"):
+            e = e.detach().cpu().numpy()
+        with np.errstate(over="ignore"):
+            v = np.asarray(e, dtype=np.float64).astype(np.float32)
+        if v.ndim != 1:
+            raise _lib.ArgumentError(f"edges of dimension {k} must be a vector, got size {v.shape}")
+        if v.size < 2:
+            raise _lib.ArgumentError(f"edges of dimension {k}: fewer than 2 edges")
+        if v.size > HIST_MAX_BINS + 1:
+            raise _lib.ArgumentError(f"edges of dimension {k}: more than {HIST_MAX_BINS + 1} edges")
+        if np.any(np.isnan(v)):
+            raise _lib.ArgumentError(f"edges of dimension {k} hold NaN")
+        if not np.all(v[1:] > v[:-1]):
+            raise _lib.ArgumentError(f"edges of dimension {k} are not strictly increasing as Float32")
+        edges.append(v)
+        bins[k] = v.size - 1
+    return edges, bins
+
+
+def _histogram_requests(keep, bins):
+    """``keep`` → sorted, distinct tuples ``(a,)`` / ``(a, b)`` with a < b, 1-D tables first
+    (the order of :func:`pdf_marginals`); ``None``: every dimension with bins, then every pair."""
+    d = len(bins)
+    if keep is None:
+        xs = [k for k in range(d) if bins[k] > 0]
+        keep = [(a,) for a in xs] + [(a, b) for i, a in enumerate(xs) for b in xs[i + 1:]]
+    out = set()
+    for K in keep:
+        K = (int(K),) if np.ndim(K) == 0 else tuple(int(v) for v in K)
+        if len(K) > 2:
+            raise _lib.UnsupportedError(f"a histogram keeps at most two dimensions, got {K}")
+        if len(K) == 0 or len(set(K)) != len(K) or any(v < 0 or v >= d for v in K):
+            raise _lib.ArgumentError(f"kept dimensions must be one or two distinct numbers in [0, {d}), got {K}")
+        if any(bins[v] == 0 for v in K):
+            raise _lib.ArgumentError(f"keep {K} names a dimension without edges")
+        out.add(tuple(sorted(K)))
+    out = sorted(out, key=lambda K: (len(K), K))
+    if not out:
+        raise _lib.ArgumentError("no histogram tables: keep is empty or no dimension has edges")
+    if len(out) > HIST_MAX_TABLES:
+        raise _lib.UnsupportedError(f"at most {HIST_MAX_TABLES} histogram tables per call, got {len(out)}")
+    return out
+
+
+def _histogram_tables(flat, M: int, reqs, bins):
+    """The (M, T) int32 blocks (numpy or tensor) → ``{K: (M, L_a) or (M, L_a, L_b)}`` views."""
+    res, at = {}, 0
+    for K in reqs:
+        if len(K) == 1:
+            size = int(bins[K[0]])
+            res[K] = flat[:, at:at + size]
+        else:
+            la, lb = int(bins[K[0]]), int(bins[K[1]])
+            size = la * lb
+            t = flat[:, at:at + size].reshape(M, lb, la)          # the lower dimension runs fastest
+            res[K] = t.transpose(0, 2, 1) if isinstance(t, np.ndarray) else t.permute(0, 2, 1)
+        at += size
+    return res
+
+
+def draw_histograms(draws, edges, keep=None, device=None):
+    """The 1-D and 2-D marginal histograms of every point's draws, counted on the device
+    (``df_draw_histograms``) → ``{(a,): (M, L_a), (a, b): (M, L_a, L_b)}`` in int32, keys sorted
+    (1-D tables first), the shape convention of ``np.histogram2d`` and of :func:`pdf_marginals`;
+    numpy arrays for numpy draws and device tensors otherwise.  ``draws`` is a numpy
+    ``(M, N, d)`` Float32 array or a device tensor of that shape in C order (the layout of
+    ``draws_out``); ``N`` a multiple of 4, ``d <= 64``.  ``edges``: the per-dimension entries of
+    :func:`histogram_edges`.  ``keep``: the tables wanted, each one dimension or a pair (sorted,
+    duplicates merged); ``None`` is the corner plot, every dimension with edges and every pair of
+    them.  The counts are ``np.histogram`` / ``np.histogram2d`` of the same Float32 draws bit for
+    bit: bin j holds ``e_j <= v < e_{j+1}``, the last bin also ``v == e_L``; draws outside, and
+    NaN, are counted nowhere in the tables that keep the dimension."""
+    import torch
+
+    from .hip import run_draw_histograms
+
+    was_np = not isinstance(draws, torch.Tensor)
+    if was_np:
+        draws = np.asarray(draws)
+        if draws.dtype != np.float32:
+            raise _lib.ArgumentError(f"draws must be Float32 (got {draws.dtype})")
+    elif draws.dtype != torch.float32:
+        raise _lib.ArgumentError(f"draws must be Float32 (got {draws.dtype})")
+    if len(draws.shape) != 3:
+        raise _lib.DimensionMismatch(f"draws must have size (M, N, d), got {tuple(draws.shape)}")
+    M, N, d = (int(v) for v in draws.shape)
+    if not 1 <= d <= 64:
+        raise _lib.ArgumentError("d must be in 1 .. 64")
+    if N <= 0 or N % 4 != 0:
+        raise _lib.ArgumentError("n_draws must be a positive multiple of 4")
+    if N > MAX_CHUNK:
+        raise _lib.UnsupportedError("a point has at most 2^24 draws (n_draws)")
+    ev, bins = histogram_edges(edges, d)
+    reqs = _histogram_requests(keep, bins)
+    T = sum(int(np.prod([bins[k] for k in K])) for K in reqs)
+    if was_np:
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        xs = torch.from_numpy(np.ascontiguousarray(draws)).to(dev)
+    else:
+        xs = draws.contiguous()
+        if xs.device.type != "cuda":
+            xs = xs.to(torch.device("cuda", torch.cuda.current_device()) if device is None else device)
+        if xs.data_ptr() % 16 != 0:
+            xs = xs.clone()
+    eb = torch.from_numpy(np.concatenate([v for v in ev if v is not None])).to(xs.device)
+    out = torch.empty((M, T), dtype=torch.int32, device=xs.device)
+    if M > 0:
+        run_draw_histograms(xs, d, M, N, eb, bins, reqs, out)
+    if was_np:
+        torch.cuda.synchronize(xs.device)
+        return _histogram_tables(out.cpu().numpy(), M, reqs, bins)
+    return _histogram_tables(out, M, reqs, bins)
+
+
+class PointHistograms:
+    """What :func:`posterior_histograms` returns: ``counts``, the dict
+    ``{(a,): (M, L_a), (a, b): (M, L_a, L_b)}`` of int32 numpy arrays over the M = prod(dims)
+    conditions (flat, first of ``dims`` fastest), ``edges`` (d Float32 vectors, ``None`` for a
+    dimension without bins), ``n_draws`` and ``dims``."""
+
+    def __init__(self, counts, edges, n_draws: int, dims=()):
+        self.counts, self.edges, self.n_draws, self.dims = counts, edges, int(n_draws), tuple(dims)
+
+    @staticmethod
+    def _key(K):
+        return (int(K),) if np.ndim(K) == 0 else tuple(int(v) for v in K)
+
+    def inside(self, K) -> np.ndarray:
+        """The number of draws inside the table's range per condition, int64 (M,): its sum."""
+        c = self.counts[self._key(K)]
+        return c.reshape(c.shape[0], -1).sum(axis=1, dtype=np.int64)
+
+    def density(self, K) -> np.ndarray:
+        """``counts / (n_draws · bin width)`` (1-D) or ``/ (n_draws · bin area)`` (2-D) in
+        float64: it integrates to the inside fraction ``inside(K) / n_draws``.  A bin with an
+        infinite edge has density 0."""
+        K = self._key(K)
+        w = np.diff(self.edges[K[0]].astype(np.float64))
+        if len(K) == 2:
+            w = w[:, None] * np.diff(self.edges[K[1]].astype(np.float64))[None, :]
+        return self.counts[K].astype(np.float64) / (float(self.n_draws) * w)
+
+    def pooled(self, K) -> np.ndarray:
+        """The table summed over the conditions, int64."""
+        return self.counts[self._key(K)].sum(axis=0, dtype=np.int64)
+
+    def __repr__(self):
+        return f"PointHistograms(tables={len(self.counts)}, dims={self.dims}, n_draws={self.n_draws})"
+
+
+def posterior_histograms(flow: Flow, theta=None, edges=None, keep=None, n_draws: int = 1024, chunk: int = 0,
+                         rng=None, seed: Optional[int] = None, offset: int = 0, dims=None,
+                         return_draws: bool = False):
+    """The 1-D and 2-D marginal histograms of ``n_draws`` samples of ``q(. | θ_j)`` for every
+    condition — the corner plot — one library call (``df_flow_point_histograms``; every chain
+    class): the draws are made and counted on the device, only the integer tables reach the host
+    → :class:`PointHistograms`.  ``edges`` and ``keep`` as for :func:`draw_histograms`; ``theta``,
+    ``dims``, ``n_draws``, ``chunk`` and the seed arguments, their checks and the draws are those
+    of :func:`posterior_quantiles` at the same ``(seed, offset)``.  With ``return_draws=True`` the
+    value is ``(histograms, draws)``, the draws numpy ``(M, n_draws, d)``.  The counts are exact
+    and bitwise reproducible, whatever the chunk."""
+    import torch
+
+    dims = _check_point_draws(flow, None, theta, n_draws, chunk, dims)
+    if edges is None:
+        raise _lib.ArgumentError("posterior_histograms needs edges: one entry per dimension")
+    d, N = flow.d, int(n_draws)
+    ev, bins = histogram_edges(edges, d)
+    reqs = _histogram_requests(keep, bins)
+    T = sum(int(np.prod([bins[k] for k in K])) for K in reqs)
+    seed = _draw_seed(rng, seed)
+    h = flow.hip()
+    dev = h.device
+    M = int(np.prod(dims)) if dims else 1
+    counts = torch.empty((M, T), dtype=torch.int32, device=dev)
+    draws = torch.empty(M * N * d, dtype=torch.float32, device=dev) if return_draws else None
+    eb = torch.from_numpy(np.concatenate([v for v in ev if v is not None])).to(dev)
+    with torch.cuda.device(dev):
+        thb = None
+        if flow.n > 0:
+            if isinstance(theta, tuple):
+                thb = torch.empty(flow.n * M, dtype=torch.float32, device=dev)
+                h.run_theta_broadcast(thb, _theta_vector(theta, dev), M)
+            else:
+                thb, _, _ = as_julia_device(theta, flow.n, dev, "θ")
+        if M > 0:
+            h.run_point_histograms(thb, M, N, int(chunk), seed, int(offset), eb, bins, reqs, counts, draws)
+        torch.cuda.synchronize(dev)
+    res = PointHistograms(_histogram_tables(counts.cpu().numpy(), M, reqs, bins), ev, N, dims)
+    if return_draws:
+        return res, draws.cpu().numpy().reshape(M, N, d)
+    return res
 
 
 def pdf(flow: Flow, x, theta=None):

@@ -21,7 +21,8 @@ import numpy as np
 from . import _lib
 from .layers import (CouplingBlock, NICECouplingLayer, NormalizationLayer, RNVPCouplingLayer)
 
-__all__ = ["HIPChain", "flatten_elements", "as_julia_device", "julia_empty", "chain_dims", "run_order_statistics"]
+__all__ = ["HIPChain", "flatten_elements", "as_julia_device", "julia_empty", "chain_dims", "run_order_statistics",
+           "run_draw_histograms"]
 
 
 def _torch():
@@ -205,6 +206,33 @@ def run_order_statistics(xs, d: int, n_points: int, n_draws: int, orders, out):
     with torch.cuda.device(xs.device):
         _lib.check(lib.df_order_statistics(_ptr(xs), C.c_int(d), C.c_int64(n_points), C.c_int64(n_draws), arr,
                                            C.c_int(nq), _ptr(out), _stream(xs.device)), "order_statistics")
+
+
+def _tables_arrays(bins, keep):
+    """(ctypes int32 bins or None, ctypes int32 requests or None, table count) of host integers:
+    ``keep`` holds one tuple ``(a,)`` or ``(a, b)`` per table."""
+    if bins is None or keep is None:
+        return None, None, 0
+    b = [int(v) for v in bins]
+    flat = [int(v) for k in keep for v in (tuple(k) + (-1,))[:2]]
+    return (C.c_int32 * max(len(b), 1))(*b), (C.c_int32 * max(len(flat), 2))(*flat), len(keep)
+
+
+def run_draw_histograms(xs, d: int, n_points: int, n_draws: int, edges, bins, keep, counts):
+    """df_draw_histograms: the 1-D and 2-D tables ``keep`` (host tuples ``(a,)`` / ``(a, b)``,
+    a < b) of the ``n_points`` points of the device tensor ``xs`` (d, n_points · n_draws; draw j of
+    point i at ``d·(i·n_draws + j)``, 16-byte aligned) into the int32 device tensor ``counts``:
+    per point a block of the tables in request order, index ``i_a + L_a·i_b``.  ``bins``: d host
+    integers; ``edges``: float32 device tensor, the ``bins[k] + 1`` edges of every dimension with
+    bins, one after the other.  On ``xs``' device and its current stream."""
+    import torch
+
+    barr, karr, nt = _tables_arrays(bins, keep)
+    lib = _lib.load()
+    with torch.cuda.device(xs.device):
+        _lib.check(lib.df_draw_histograms(_ptr(xs), C.c_int(d), C.c_int64(n_points), C.c_int64(n_draws), _ptr(edges),
+                                          barr, karr, C.c_int32(nt), _ptr(counts), _stream(xs.device)),
+                   "draw_histograms")
 
 
 class HIPChain:
@@ -392,6 +420,23 @@ class HIPChain:
     def run_order_statistics(xs, d: int, n_points: int, n_draws: int, orders, out):
         """df_order_statistics on device tensors: see :func:`run_order_statistics`."""
         run_order_statistics(xs, d, n_points, n_draws, orders, out)
+
+    def run_point_histograms(self, thbuf, n_points: int, n_draws: int, chunk: int, seed: int, offset: int, edges=None,
+                             bins=None, keep=None, countsbuf=None, drawsbuf=None):
+        """df_flow_point_histograms: the draws of :meth:`run_point_stats` counted at the end of
+        every chunk.  ``countsbuf`` (int32, n_points blocks of the tables' sizes) takes the tables
+        ``keep`` as :func:`run_draw_histograms` lays them out (``edges``, ``bins`` as there),
+        ``drawsbuf`` (d · n_points · n_draws) the draws themselves; at least one of the two."""
+        barr, karr, nt = _tables_arrays(bins, keep)
+        _lib.check(self.lib.df_flow_point_histograms(self.handle, _ptr(thbuf), C.c_int64(n_points), C.c_int64(n_draws),
+                                                     C.c_int64(chunk), C.c_uint64(seed), C.c_uint64(offset),
+                                                     _ptr(edges), barr, karr, C.c_int32(nt), _ptr(countsbuf),
+                                                     _ptr(drawsbuf), _stream(self.device)), "point_histograms")
+
+    @staticmethod
+    def run_draw_histograms(xs, d: int, n_points: int, n_draws: int, edges, bins, keep, counts):
+        """df_draw_histograms on device tensors: see :func:`run_draw_histograms`."""
+        run_draw_histograms(xs, d, n_points, n_draws, edges, bins, keep, counts)
 
     def run_sample_region(self, xbuf, thvec, n_want: int, lo, hi, A, b, max_tries: int, round: int, seed: int,
                           offset: int = 0):

@@ -403,6 +403,72 @@ int df_flow_point_quantiles(df_chain* chain, const float* x, const float* theta_
                             int n_orders, float* quant_out, int32_t* rank_out, double* sums_out, float* draws_out,
                             void* stream);
 
+/* ---- posterior histograms: 1-D and 2-D marginal counts per point (additive to ABI 5) ----
+ * The corner plot of q(. | θ_i) from its draws: integer counts, exact and bitwise reproducible
+ * however the work is split (no floating-point atomic anywhere).
+ *
+ * df_draw_histograms: the counting alone, on the current device (as df_order_statistics).
+ *   xs (d, n_points·n_draws) DEVICE, 16-byte aligned, draw j of point i at xs + d·(i·n_draws + j);
+ *   bins: HOST, d int32; bins[k] = L_k bins of dimension k, 0: no edges, no table may keep it;
+ *   edges: DEVICE Float32, the L_k + 1 edges of every dimension with L_k > 0, one after the
+ *          other in dimension order.  The call does not read them (that would synchronise):
+ *          they are expected strictly increasing without NaN.  For any content (unsorted, equal,
+ *          NaN) every add lands inside the point's own block or is dropped;
+ *   keep: HOST, n_tables requests of two int32 as df_flow_pdf_marginals takes them: {a, -1} the
+ *         1-D table of dimension a, {a, b} with a < b the 2-D table; requests are distinct.
+ *         bins and keep are read at call time and reach the kernel by value: no copy, no
+ *         synchronisation, capturable;
+ *   counts_out: DEVICE int32, point i owns a block of T = Σ_j size_j words, size_j = L_a or
+ *         L_a·L_b; table j sits behind the tables before it (request order), the lower-numbered
+ *         kept dimension runs fastest: index i_a + L_a·i_b.
+ * Bin rule (numpy's for explicit edges): bin j, 0 <= j < L, holds e_j <= v < e_{j+1}, the last
+ * bin also v == e_L; Float32 comparisons, −0 equals +0, ±inf are ordinary values and an
+ * infinite edge is allowed.  A draw below e_0, above e_L or NaN is counted nowhere in the
+ * tables that keep that dimension (a table's sum is its inside count); a 2-D table counts a
+ * draw when both coordinates are inside.  The counts equal np.histogram / np.histogram2d of the
+ * same Float32 draws bit for bit.
+ * One kernel (df_hist.hip): tables and edges in LDS, a branch-free binary search of 8 steps per
+ * kept dimension, integer LDS adds, one flush per (point, group of tables); a wave per point up
+ * to n_draws = 256 and a workgroup per point above, plain stores of every word (zero bins
+ * included), nothing zeroed, no global atomics.  Above n_draws = DF_HIST_SPLIT_DRAWS a point's
+ * draws are divided among ceil(n_draws / DF_HIST_SPLIT_DRAWS) workgroups: the blocks are zeroed
+ * on the stream and the partial tables merge with integer global atomic adds — the same bytes.
+ * (The environment variable DF_HIST_SPLIT_DRAWS, a multiple of 256 above 256, overrides the
+ * threshold at call time: a tuning aid, the counts do not depend on it.)
+ * What does not fit the LDS at once (at most 64 KiB of tables: one 128 x 128 table) is walked
+ * in groups of tables planned on the host (df_hist_plan.cpp); every group reads the draws again.
+ * Checked in this order before any device work, also for an empty call: 1 <= d <= 64
+ * (DF_ERR_INVALID); n_points >= 0 (DF_ERR_SHAPE); n_draws a positive multiple of 4
+ * (DF_ERR_INVALID) and at most 2^24 (DF_ERR_UNSUPPORTED); xs, counts_out, edges, bins, keep
+ * non-null and xs 16-byte aligned (DF_ERR_INVALID); 1 <= n_tables <= DF_HIST_MAX_TABLES
+ * (DF_ERR_UNSUPPORTED); every bins[k] in [0, DF_HIST_MAX_BINS] (negative: DF_ERR_INVALID, above:
+ * DF_ERR_UNSUPPORTED; the message names k); every request well formed — first index in [0, d),
+ * second −1 or in (first, d), both of dimensions with bins > 0, no request repeated
+ * (DF_ERR_INVALID, the message names the request); T within int32 and T·n_points within int64
+ * (DF_ERR_SHAPE).  Then n_points == 0: DF_OK, nothing launched, nothing written.
+ *
+ * df_flow_point_histograms: df_flow_point_stats' chunk loop with the counting at the end of
+ * every chunk.  The draws, the θ repeat, the chunking by whole points, the workspaces, the
+ * counters (offset + d·i·n_draws/4) and the rules and messages for the chain, n_points, n_draws,
+ * chunk, θ and the bounds are df_flow_point_stats': draw j of point i is bitwise the draw that
+ * call makes at the same (seed, offset), and draws_out (optional) is bitwise its copy.
+ * counts_out may be NULL when draws_out is given; edges, bins, keep and n_tables are then
+ * ignored.  Both NULL is DF_ERR_INVALID.  The table rules above are checked after the outputs.
+ * Calls on one chain must not overlap on different streams (the workspaces are the chain's).
+ * No host synchronisation; capturable once the workspaces are warm. */
+#define DF_HIST_MAX_BINS 128    /* bins per dimension: one 128 x 128 table is 64 KiB of LDS */
+#define DF_HIST_MAX_TABLES 2080 /* 64 + 64·63/2: the full corner at d = 64 */
+#define DF_HIST_SPLIT_DRAWS 2048 /* draws of a point per workgroup above this n_draws */
+
+int df_draw_histograms(const float* xs, int d, int64_t n_points, int64_t n_draws, const float* edges,
+                       const int32_t* bins, const int32_t* keep, int32_t n_tables, int32_t* counts_out,
+                       void* stream);
+
+int df_flow_point_histograms(df_chain* chain, const float* theta_raw, int64_t n_points, int64_t n_draws,
+                             int64_t chunk, uint64_t seed, uint64_t offset, const float* edges,
+                             const int32_t* bins, const int32_t* keep, int32_t n_tables, int32_t* counts_out,
+                             float* draws_out, void* stream);
+
 /* ---- grid logpdf------------------------------------------------------------
  * logpdf(flow, (x_1, ..., x_d), (θ_1, ..., θ_n)) (src/Flows.jl:287-331; pdf, :348-349, is
  * its exp): the log-density on the outer product of one vector per dimension, generated on
