@@ -679,12 +679,17 @@ __device__ __forceinline__ void dense_first_split_pf(const bf16x8 (&w)[HT], cons
         // one value per tile, split on its own: each plane is the low half of its
         // conversion, so a remainder takes a shift and a subtract (a pair of two tiles'
         // values needs a mask for the high half as well); the planes are split2's
-        bf16x2 h, m, l;
-        h = bf16x2{(__bf16)xin[t][0], z};
+        // The second remainder takes m from the operand's own word (m, h), whose low half
+        // it is: r1 is converted once, with that word.
+        const bf16x2 h = bf16x2{(__bf16)xin[t][0], z};
         const float r1 = split_rem<0>(h, xin[t][0]);
-        m = bf16x2{(__bf16)r1, z};
-        l = bf16x2{(__bf16)split_rem<0>(m, r1), z};
-        b[t] = bf16x8{h[0], m[0], h[0], l[0], m[0], h[0], z, z};
+        // (the word is made opaque: left alone the compiler converts r1 a second time, with a
+        // zero, for the remainder)
+        uint32_t w = __builtin_bit_cast(uint32_t, bf16x2{(__bf16)r1, (__bf16)xin[t][0]});
+        asm("" : "+v"(w));
+        const bf16x2 mh = __builtin_bit_cast(bf16x2, w);
+        const __bf16 l = (__bf16)split_rem<0>(mh, r1);
+        b[t] = bf16x8{(__bf16)xin[t][0], (__bf16)r1, (__bf16)xin[t][0], l, mh[0], mh[1], z, z};
     }
 #pragma unroll
     for (int m = 0; m < HT; ++m)
@@ -700,14 +705,38 @@ __device__ __forceinline__ void out_row_request(const uint8_t* w3g, int oo, f32x
     for (int kq = 0; kq < HT; ++kq) w[kq] = lds4(w3g + ((oo * 16 * HT + 16 * kq) << 2));
 }
 
-// How many (row, output) pairs a lane group owns after the tail's transposed reduction.
-// The reduction has four slots.  A group of two tiles with NO <= 2 outputs fills them with
-// BOTH tiles' outputs, so one tree, one coupling and one ldj update serve the two tiles:
-//   NO = 2: lane group g owns output g & 1 of tile g >> 1;
-//   NO = 1: lane group g owns the output of tile g & 1 (groups 2, 3 hold copies of 0, 1:
-//           they compute and store the same bits to the same words, no lane is masked).
-// Otherwise every tile has its own tree and group g owns output g of each of the TT tiles.
-constexpr int split_tail_rows(int TT, int NO) { return (TT == 2 && NO <= 2) ? 1 : TT; }
+// What a lane group owns after the tail's transposed reduction.  A reduction tree has four
+// slots, one per lane group.  The pair form (split_tail_pair) fills every tree with BOTH
+// tiles' outputs of a group of two tiles; every lane takes part in the couplings (copies
+// compute and store the same bits to the same words), and ONE ldj update serves both rows:
+//   NO = 1: one tree, lane group g owns the output of tile g & 1 (groups 2, 3: copies);
+//   NO = 2: one tree, lane group g owns output g & 1 of tile g >> 1;
+//   NO = 3: two trees: in the first lane group g owns output g & 1 of tile g >> 1, in the
+//           second output 2 of tile g & 1 (groups 2, 3: copies), so a lane group's two
+//           values may lie in two tiles; Σ s of tile 0 ends in lane group 0, of tile 1 in
+//           lane group 3, which update the ldj words of their first tree's tile;
+//   NO = 4: two trees, lane group g owns outputs g & 1 and 2 + (g & 1) of tile g >> 1.
+// Otherwise every tile has its own tree and lane group g owns output g of each of the TT
+// tiles (TT rows, one value per row; groups g >= NO are masked, lane group 0 updates ldj).
+// Three and four outputs take the pair form where the lane group's offsets are values held
+// across the bodies (WIDE = LANES of net_tiles): derived in every body, the second tree's
+// words and columns cost more than the form saves.
+constexpr bool split_tail_pair(int TT, int NO, bool WIDE) { return TT == 2 && (NO <= 2 || WIDE); }
+// The values a lane group owns and its row offsets: in the pair form the one of the group's
+// first tile, and the tile a value lies in is part of the value's column (SplitTail).
+constexpr int split_tail_vals(int TT, int NO, bool WIDE) { return split_tail_pair(TT, NO, WIDE) ? (NO + 1) / 2 : TT; }
+constexpr int split_tail_rows(int TT, int NO, bool WIDE) { return split_tail_pair(TT, NO, WIDE) ? 1 : TT; }
+
+// One tree on the slots (a0, a1, b0, b1): lane groups 0..3 get the sums of a0, a1, b0, b1
+// over the four lane groups, each associated ((p_g0 + p_g1) + (p_g2 + p_g3)).
+__device__ __forceinline__ float pair_tree(float a0, float a1, float b0, float b1) {
+    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(a0), __float_as_uint(a1), false, false);
+    const float A = __uint_as_float(a[0]) + __uint_as_float(a[1]);  // a0 g01, a1 g01, a0 g23, a1 g23
+    auto b = __builtin_amdgcn_permlane16_swap(__float_as_uint(b0), __float_as_uint(b1), false, false);
+    const float Bv = __uint_as_float(b[0]) + __uint_as_float(b[1]);  // b0 g01, b1 g01, b0 g23, b1 g23
+    auto c = __builtin_amdgcn_permlane32_swap(__float_as_uint(A), __float_as_uint(Bv), false, false);
+    return __uint_as_float(c[0]) + __uint_as_float(c[1]);
+}
 
 // What a read-ahead SPLIT body and the ldj update behind it (uniform_kernel's tiles_loop)
 // share: ce, the state column of ldj_elem (ldj_chain is the column before it), goes in;
@@ -716,9 +745,12 @@ constexpr int split_tail_rows(int TT, int NO) { return (TT == 2 && NO <= 2) ? 1 
 // l16, g16: the lane's two offsets into fragments and vectors, lane · 16 and (lane >> 4) · 16,
 // from the kernel where the instance has the registers to hold them across bodies (LANES
 // of net_tiles); otherwise the body derives them from an opaque copy of the thread id.
+// ts, the offset from a tile's rows to the next tile's, goes in as well; lcol comes out: ce,
+// in the pair form plus ts where the lane group's ldj words are the second tile's.
 template <int TT>
 struct SplitTail {
-    int ce, l16, g16;
+    int ce, ts, l16, g16;
+    int lcol;
     int row[TT];
     float e_old[TT], a_old[TT];
 };
@@ -726,16 +758,19 @@ struct SplitTail {
 // out_valu_t on two sets of weight vectors: output 0's (w0, with the bias bo and the
 // coupling's slot word) were requested by the caller before the second relu; output
 // oo + 1's are requested ahead of output oo's 4·HT·TT fma, the coupling's old state
-// values (state[row[u] + aslot] -> v) and, LDJ, the rows' ldj words (tl) with output 1's.
+// values (state[row + aslot[u]] -> v[u]) and, LDJ, the rows' ldj words (tl) with output 1's.
 // fma order (oo, kq, r) as in out_valu_t; the swap reduction as in out_valu_t per tile, or
-// one tree for both tiles (split_tail_rows): every sum still associates
+// trees that hold both tiles (split_tail_vals): every sum still associates
 // ((p_g0 + p_g1) + (p_g2 + p_g3)), as outputs 2, 3 of a four-output net do in their slots.
-template <int HT, int TT, int NO, bool LDJ, int NU>
-__device__ __forceinline__ void out_valu_t_pf(const uint8_t* w3g, const f32x4 (&w0)[HT], float bo,
-                                              const f32x4 (&h)[TT][HT], const float* state, const int& aslot,
+// bo[u], aslot[u]: the bias and the state column of the u-th output the lane group owns.
+template <int HT, int TT, int NO, bool LDJ, bool WIDE, int NU>
+__device__ __forceinline__ void out_valu_t_pf(const uint8_t* w3g, const f32x4 (&w0)[HT], const float (&bo)[NU],
+                                              const f32x4 (&h)[TT][HT], const float* state, const int (&aslot)[NU],
                                               SplitTail<TT>& tl, float (&v)[NU], float (&y)[NU]) {
     static_assert(NO >= 1 && NO <= 4, "FAST tails: 1..4 outputs");
-    static_assert(NU == split_tail_rows(TT, NO), "rows a lane group owns");
+    static_assert(NU == split_tail_vals(TT, NO, WIDE), "outputs a lane group owns");
+    constexpr bool PAIR = split_tail_pair(TT, NO, WIDE);
+    constexpr int NR = split_tail_rows(TT, NO, WIDE);
     float p[TT][4];
 #pragma unroll
     for (int t = 0; t < TT; ++t)
@@ -750,11 +785,12 @@ __device__ __forceinline__ void out_valu_t_pf(const uint8_t* w3g, const f32x4 (&
         lds_wait0();
         if (oo == 0) {
 #pragma unroll
-            for (int u = 0; u < NU; ++u) {
-                v[u] = state[tl.row[u] + aslot];
-                if constexpr (LDJ) {  // a word whose value the update does not use is read for nothing
-                    tl.e_old[u] = state[tl.row[u] + tl.ce];
-                    tl.a_old[u] = state[tl.row[u] + tl.ce - 1];
+            for (int u = 0; u < NU; ++u) v[u] = state[tl.row[NR == 1 ? 0 : u] + aslot[u]];
+            if constexpr (LDJ) {  // a word whose value the update does not use is read for nothing
+#pragma unroll
+                for (int r = 0; r < NR; ++r) {
+                    tl.e_old[r] = state[tl.row[r] + tl.lcol];
+                    tl.a_old[r] = state[tl.row[r] + tl.lcol - 1];
                 }
             }
         }
@@ -770,7 +806,17 @@ __device__ __forceinline__ void out_valu_t_pf(const uint8_t* w3g, const f32x4 (&
 #pragma unroll
         for (int t = 0; t < TT; ++t) asm volatile("" : "+v"(p[t][oo]));
     }
-    if constexpr (NU < TT) {  // one tree: the slots hold both tiles
+    if constexpr (PAIR && NO >= 3) {  // two trees, both tiles in each (split_tail_pair)
+        y[0] = pair_tree(p[0][0], p[0][1], p[1][0], p[1][1]) + bo[0];  // output g & 1 of tile g >> 1
+        if constexpr (NO == 4) {
+            y[1] = pair_tree(p[0][2], p[0][3], p[1][2], p[1][3]) + bo[1];  // output 2 + (g & 1) of tile g >> 1
+        } else {  // output 2 of both tiles through one swap, as the one-output tree
+            auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(p[0][2]), __float_as_uint(p[1][2]), false, false);
+            const float A = __uint_as_float(a[0]) + __uint_as_float(a[1]);  // t0 g01, t1 g01, t0 g23, t1 g23
+            auto c = __builtin_amdgcn_permlane32_swap(__float_as_uint(A), __float_as_uint(A), false, false);
+            y[1] = (__uint_as_float(c[0]) + __uint_as_float(c[1])) + bo[1];  // output 2 of tile g & 1
+        }
+    } else if constexpr (PAIR) {  // one tree: the slots hold both tiles
         const float q = NO == 2 ? p[0][1] : p[1][0];
         auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(p[0][0]), __float_as_uint(q), false, false);
         const float A = __uint_as_float(a[0]) + __uint_as_float(a[1]);  // NO = 2, tile 0: p0 g01, p1 g01, p0 g23, p1 g23
@@ -780,7 +826,7 @@ __device__ __forceinline__ void out_valu_t_pf(const uint8_t* w3g, const f32x4 (&
             Bv = __uint_as_float(b[0]) + __uint_as_float(b[1]);           // tile 1: p0 g01, p1 g01, p0 g23, p1 g23
         }
         auto c = __builtin_amdgcn_permlane32_swap(__float_as_uint(A), __float_as_uint(Bv), false, false);
-        y[0] = (__uint_as_float(c[0]) + __uint_as_float(c[1])) + bo;      // split_tail_rows: the group's (tile, output)
+        y[0] = (__uint_as_float(c[0]) + __uint_as_float(c[1])) + bo[0];   // split_tail_vals: the group's (tile, output)
     } else {
 #pragma unroll
         for (int t = 0; t < TT; ++t) {
@@ -792,7 +838,7 @@ __device__ __forceinline__ void out_valu_t_pf(const uint8_t* w3g, const f32x4 (&
                 Bv = __uint_as_float(b[0]) + __uint_as_float(b[1]);             // p2 g01, p3 g01, p2 g23, p3 g23
             }
             auto c = __builtin_amdgcn_permlane32_swap(__float_as_uint(A), __float_as_uint(Bv), false, false);
-            y[t] = (__uint_as_float(c[0]) + __uint_as_float(c[1])) + bo;      // group g: output g
+            y[t] = (__uint_as_float(c[0]) + __uint_as_float(c[1])) + bo[t];   // group g: output g
         }
     }
 }
@@ -831,7 +877,8 @@ __device__ __forceinline__ void split_prio() {
 // coupling phase; sum[t] = Σ_k s_k for s phases (row order).
 // hd: the read-ahead SPLIT path's scalar words (SplitHead); unused by every other path.
 // tl, LDJ: that path's tail (SplitTail); there sum[u] belongs to row tl.row[u],
-// u < split_tail_rows(TT, NO), and LDJ asks an s phase for the rows' ldj words.
+// u < split_tail_rows(TT, NO, LANES), at column tl.lcol, and LDJ asks an s phase for the
+// rows' ldj words.
 template <int HT, int TT, bool OUTV, bool RELU, int PH, bool FAST = false, int NO = 0, bool SPLIT = false,
           bool LDJ = false, bool LANES = false>
 __device__ __forceinline__ void net_tiles(const uint8_t* buf, const UNet& N, const ULayer& L, const int32_t* tab,
@@ -887,44 +934,74 @@ __device__ __forceinline__ void net_tiles(const uint8_t* buf, const UNet& N, con
         split_prio<false>();
         f32x4 wo[HT];
         out_row_request<HT, NO>(w3g, 0, wo);
-        // the (row, output) this lane group owns after the reduction (split_tail_rows)
-        constexpr int NU = split_tail_rows(TT, NO);
-        constexpr bool ONE_TREE = NU < TT;
-        const int go = ONE_TREE ? (NO == 2 ? (g & 1) : 0) : (g < NO ? g : 0);
-        const float bo = reinterpret_cast<const float*>(w3)[NO * 16 * HT + go];
-        const int aslot = ((uint32_t)hd.af_word >> (kSplitSlotBits * go)) & ((1 << kSplitSlotBits) - 1);
-        if constexpr (ONE_TREE) {
-            // (an offset, not a choice between ro[0] and ro[1]: that is an indexed read of
-            // ro, which then lives in scratch)
-            tl.row[0] = ro[0] + ((NO == 2 ? (g >> 1) : (g & 1)) ? ro[1] - ro[0] : 0);
+        // the row and the outputs this lane group owns after the reduction (split_tail_vals)
+        constexpr int NU = split_tail_vals(TT, NO, LANES);
+        constexpr int NR = split_tail_rows(TT, NO, LANES);
+        constexpr bool PAIR = split_tail_pair(TT, NO, LANES);
+        const float* bias = reinterpret_cast<const float*>(w3) + NO * 16 * HT;
+        float bo[NU];
+        int aslot[NU];
+        tl.lcol = tl.ce;
+        if constexpr (PAIR) {
+            // The lane group's tile as an offset (the tile step or 0) that goes into its
+            // columns, not into the row: column and offset are values of the lane group and
+            // the net alone, so their sum leaves the tile-group loop where the lane group's
+            // offsets are held across the bodies.  (Not a choice between ro[0] and ro[1]
+            // either: that is an indexed read of ro, which then lives in scratch.)
+            const int go = NO == 1 ? 0 : (g & 1);
+            const int t0 = (NO == 1 ? (g & 1) : (g >> 1)) ? tl.ts : 0;
+            bo[0] = bias[go];
+            aslot[0] = (((uint32_t)hd.af_word >> (kSplitSlotBits * go)) & ((1 << kSplitSlotBits) - 1)) + t0;
+            tl.lcol = tl.ce + t0;
+            if constexpr (NO == 3) {  // output 2, of tile g & 1: a uniform word and column
+                bo[1] = bias[2];
+                aslot[1] = (((uint32_t)hd.af_word >> (kSplitSlotBits * 2)) & ((1 << kSplitSlotBits) - 1)) +
+                           (go ? tl.ts : 0);
+            } else if constexpr (NO == 4) {
+                bo[1] = bias[go + 2];
+                aslot[1] = (((uint32_t)hd.af_word >> (kSplitSlotBits * (go + 2))) & ((1 << kSplitSlotBits) - 1)) + t0;
+            }
+            tl.row[0] = ro[0];
         } else {
+            const int go = g < NO ? g : 0;
 #pragma unroll
-            for (int t = 0; t < TT; ++t) tl.row[t] = ro[t];
+            for (int t = 0; t < TT; ++t) {
+                bo[t] = bias[go];
+                aslot[t] = ((uint32_t)hd.af_word >> (kSplitSlotBits * go)) & ((1 << kSplitSlotBits) - 1);
+                tl.row[t] = ro[t];
+            }
         }
         sched_fence();
         bias_act<HT, TT, true>(buf, DF_ACT_RELU, B, false);
         float v[NU], y[NU];
-        out_valu_t_pf<HT, TT, NO, SPH && LDJ>(w3g, wo, bo, B, state, aslot, tl, v, y);
-        // one region for the lane groups that own an output (all of them with one tree), so
-        // that the tiles' couplings interleave
-        if (ONE_TREE || g < NO) {
+        out_valu_t_pf<HT, TT, NO, SPH && LDJ, LANES>(w3g, wo, bo, B, state, aslot, tl, v, y);
+        // one region for the lane groups that own an output (all of them when the trees hold
+        // both tiles), so that the couplings interleave
+        if (PAIR || g < NO) {
 #pragma unroll
-            for (int u = 0; u < NU; ++u) state[tl.row[u] + aslot] = couple1<PH>(v[u], y[u]);
+            for (int u = 0; u < NU; ++u) state[tl.row[NR == 1 ? 0 : u] + aslot[u]] = couple1<PH>(v[u], y[u]);
         }
+        if constexpr (!SPH) {
 #pragma unroll
-        for (int u = 0; u < NU; ++u) {
-            if constexpr (!SPH) {
-                sum[u] = 0.f;
-            } else if constexpr (ONE_TREE && NO == 2) {
-                // y_0 + y_1 of the group's tile, in all four lane groups: the row's ldj update
-                // needs no mask (group_row_sum's y + a[1] in groups 0 and 2, where y = a[0])
-                auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(y[u]), __float_as_uint(y[u]), false, false);
-                sum[u] = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-            } else if constexpr (ONE_TREE) {
-                sum[u] = y[u];
-            } else {
-                sum[u] = group_row_sum<NO>(y[u]);  // valid in lane group 0
+            for (int t = 0; t < TT; ++t) sum[t] = 0.f;
+        } else if constexpr (PAIR && NO == 1) {
+            sum[0] = y[0];
+        } else if constexpr (PAIR) {
+            // Σ s of the group's tile in group_row_sum's order, ((y_0 + y_1) + y_2) + y_3: the
+            // swap of a tree with itself gives every lane group both outputs of its tile, so
+            // with two and four outputs all four lane groups hold their row's sum and the ldj
+            // update needs no mask; with three, y_2 is the tile's own in lane groups 0 and 3
+            auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(y[0]), __float_as_uint(y[0]), false, false);
+            float s = __uint_as_float(a[0]) + __uint_as_float(a[1]);
+            if constexpr (NO == 3) s = s + y[1];
+            if constexpr (NO == 4) {
+                auto c = __builtin_amdgcn_permlane16_swap(__float_as_uint(y[1]), __float_as_uint(y[1]), false, false);
+                s = (s + __uint_as_float(c[0])) + __uint_as_float(c[1]);
             }
+            sum[0] = s;
+        } else {
+#pragma unroll
+            for (int t = 0; t < TT; ++t) sum[t] = group_row_sum<NO>(y[t]);  // valid in lane group 0
         }
         return;
     }
@@ -1264,7 +1341,7 @@ uniform_kernel(ChainArgs a) {
 #pragma unroll
                     for (int t = 0; t < kTT; ++t) ro[t] = r0 + (tt + t) * tstep;
                     SplitTail<kTT> tl;
-                    tl.ce = cE, tl.l16 = lane16, tl.g16 = group16;
+                    tl.ce = cE, tl.ts = tstep, tl.l16 = lane16, tl.g16 = group16;
                     net_tiles<HT, kTT, OUTV, RELU, PH, FAST, NO, SPLIT, WANT_LDJ, kHoldLanes>(buf, N, L, tab, state, ro,
                                                                                               ssum, hd, tl);
                     constexpr bool SPH = (PH == impl::PH_S_FWD || PH == impl::PH_S_BWD);
@@ -1272,17 +1349,19 @@ uniform_kernel(ChainArgs a) {
                         // ldj_update on the words the body read with the coupling's old values:
                         // the same additions in the same order, the three uniform flags select
                         // between values, and no LDS round trip stands between read and write.
-                        // One tree for both tiles: every lane group holds its row's Σ s, so all
-                        // lanes store (copies write the same bits); else lane group 0 does.
-                        constexpr int NU = split_tail_rows(kTT, NO);
+                        // Pair form (split_tail_pair): every lane group holds its row's Σ s, so all
+                        // lanes store (copies write the same bits), but with three outputs, where
+                        // lane groups 0 and 3 hold the two rows' sums; else lane group 0 stores.
+                        constexpr bool PAIR = split_tail_pair(kTT, NO, kHoldLanes);
+                        constexpr int NU = split_tail_rows(kTT, NO, kHoldLanes);
                         if constexpr (WANT_LDJ) {
-                            if (NU < kTT || g == 0) {
+                            if (PAIR ? (NO != 3 || g == 0 || g == 3) : g == 0) {
 #pragma unroll
                                 for (int u = 0; u < NU; ++u) {
                                     const float l = sign * ssum[u];
                                     const float e = first_in_elem ? l : tl.e_old[u] + l;
-                                    state[tl.row[u] + cE] = e;
-                                    if (last_in_elem) state[tl.row[u] + cA] = have_acc ? tl.a_old[u] + e : e;
+                                    state[tl.row[u] + tl.lcol] = e;
+                                    if (last_in_elem) state[tl.row[u] + tl.lcol - 1] = have_acc ? tl.a_old[u] + e : e;
                                 }
                             }
                         }
