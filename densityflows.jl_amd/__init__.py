@@ -14,7 +14,9 @@ from .chains import FlowChain, backward, concatenate, forward, forward_, forward
 from .data import (DataArrays, DataPartition, MetaData, dflt_theta, maximum_theta, minimum_theta,
                    normalize_input, resize_output)
 from .flows import (HIST_MAX_BINS, HIST_MAX_TABLES, HIST_SPLIT_DRAWS, QUANT_MAX_ORDERS, Box, Flow, HalfSpaces,
-                    MvNormal, PointHistograms, PointStats, Region, ScoreMoments, credible_intervals,
+                    ImportanceWeights, MvNormal, PointHistograms, PointStats, Region, ScoreMoments,
+                    WeightedPointStats, credible_intervals, importance_posterior_stats, importance_weights,
+                    posterior_draws, weighted_moments_from_sums, weighted_stats,
                     draw_histograms, entropy, expected_coverage, fisher_information, histogram_edges, hpd_levels,
                     logpdf,
                     logpdf_grad, logpdf_grid, nll_partial_sum, order_statistics, pdf, pdf_marginals,

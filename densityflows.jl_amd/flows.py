@@ -19,7 +19,9 @@ __all__ = ["Flow", "MvNormal", "predict", "sample", "sample_logpdf", "sample_wit
            "fisher_information", "entropy", "hpd_levels", "expected_coverage", "PointStats", "posterior_stats",
            "sbc_ranks", "sbc_histogram", "QUANT_MAX_ORDERS", "quantile_orders", "order_statistics",
            "posterior_quantiles", "credible_intervals", "HIST_MAX_BINS", "HIST_MAX_TABLES", "HIST_SPLIT_DRAWS",
-           "histogram_edges", "draw_histograms", "posterior_histograms", "PointHistograms"]
+           "histogram_edges", "draw_histograms", "posterior_histograms", "PointHistograms", "posterior_draws",
+           "ImportanceWeights", "importance_weights", "WeightedPointStats", "weighted_moments_from_sums",
+           "weighted_stats", "importance_posterior_stats"]
 
 LOG2PI = float(np.log(2.0 * np.pi))
 
@@ -1448,6 +1450,295 @@ def posterior_histograms(flow: Flow, theta=None, edges=None, keep=None, n_draws:
     if return_draws:
         return res, draws.cpu().numpy().reshape(M, N, d)
     return res
+
+
+# ---------------------------------------------------------------------------
+# importance weights: evidence, effective sample size, weighted moments (df_iw.hip)
+# ---------------------------------------------------------------------------
+
+def posterior_draws(flow: Flow, theta=None, n_draws: int = 1024, dims=None, rng=None, seed: Optional[int] = None,
+                    offset: int = 0, return_logpdf: bool = True, as_tensor: bool = False):
+    """``n_draws`` samples of ``q(. | θ_i)`` for every condition together with their ``log q``, one
+    library call (``df_flow_sample_logpdf`` with θ row i repeated over its draws) → ``(draws, logq)``
+    of shapes ``(M, n_draws, d)`` and ``(M, n_draws)`` in Float32, M = prod(dims) (flat, first of
+    ``dims`` fastest): the layout :func:`weighted_stats`, :func:`order_statistics` and
+    :func:`draw_histograms` take.  Draw k of point i is sample ``i·n_draws + k`` of that call: its
+    ``log q`` is bitwise the ``draws_logpdf_out`` of ``df_flow_hpd_ranks`` at the same
+    ``(seed, offset)`` within one chain-pass kernel family.  ``theta``, ``dims``, ``n_draws`` and
+    the seed arguments and their checks are those of :func:`posterior_stats`.  With
+    ``return_logpdf=False`` the value is the draws alone; with ``as_tensor=True`` both stay on the
+    device (nothing synchronises)."""
+    import torch
+
+    dims = _check_point_draws(flow, None, theta, n_draws, 0, dims)
+    N = int(n_draws)
+    seed = _draw_seed(rng, seed)
+    h = flow.hip()
+    dev, d, n = h.device, flow.d, flow.n
+    M = int(np.prod(dims)) if dims else 1
+    draws = torch.empty((M, N, d), dtype=torch.float32, device=dev)
+    lq = torch.empty((M, N), dtype=torch.float32, device=dev) if return_logpdf else None
+    with torch.cuda.device(dev):
+        th_rep = None
+        if n > 0:
+            if isinstance(theta, tuple):
+                th_rep = torch.empty(n * M * N, dtype=torch.float32, device=dev)
+                if M > 0:
+                    h.run_theta_broadcast(th_rep, _theta_vector(theta, dev), M * N)
+            else:
+                thb, _, _ = as_julia_device(theta, n, dev, "θ")
+                th_rep = thb.view(M, n).repeat_interleave(N, dim=0).reshape(-1)
+        if M > 0:
+            h.run_sample_logpdf(draws.view(-1), lq.view(-1) if return_logpdf else None, th_rep, False, M * N, seed,
+                                int(offset))
+        if not as_tensor:
+            torch.cuda.synchronize(dev)
+    if not as_tensor:
+        draws = draws.cpu().numpy()
+        lq = lq.cpu().numpy() if return_logpdf else None
+    return (draws, lq) if return_logpdf else draws
+
+
+def _check_mn(a, name: str, shape=None):
+    """The host checks of an ``(M, N)`` Float32 array (numpy or tensor), no library call →
+    ``(M, N)``.  ``shape``: the size it must have."""
+    import torch
+
+    is_t = isinstance(a, torch.Tensor)
+    if not is_t:
+        a = np.asarray(a)
+    if a.dtype != (torch.float32 if is_t else np.float32):
+        raise _lib.ArgumentError(f"{name} must be Float32 (got {a.dtype})")
+    if len(a.shape) != 2:
+        raise _lib.DimensionMismatch(f"{name} must have size (M, N), got {tuple(a.shape)}")
+    M, N = (int(v) for v in a.shape)
+    if shape is not None and (M, N) != tuple(shape):
+        raise _lib.DimensionMismatch(f"{name} must have size {tuple(shape)}, got {(M, N)}")
+    if N <= 0 or N % 4 != 0:
+        raise _lib.ArgumentError("n_draws must be a positive multiple of 4")
+    if N > MAX_CHUNK:
+        raise _lib.UnsupportedError("a point has at most 2^24 draws (n_draws)")
+    return M, N
+
+
+def _device_rows(a, dev):
+    """A checked array as a C-contiguous, 16-byte aligned float32 device tensor of its shape."""
+    import torch
+
+    if not isinstance(a, torch.Tensor):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    t = a.contiguous()
+    if t.device.type != "cuda":
+        t = t.to(dev)
+    return t.clone() if t.data_ptr() % 16 != 0 else t
+
+
+def _default_device(*arrays):
+    import torch
+
+    for a in arrays:
+        if isinstance(a, torch.Tensor) and a.device.type == "cuda":
+            return a.device
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+class ImportanceWeights:
+    """What :func:`importance_weights` returns for M points of N draws: ``w`` ``(M, N)`` Float32, the
+    stabilised weights ``exp(logw − max)`` (numpy for numpy input, a device tensor otherwise; the
+    largest of a point is 1), and float64 numpy vectors of length M: ``log_max``,
+    ``sum_w`` = W1 = Σ w, ``sum_w2`` = W2 = Σ w², ``n_positive`` (int64) the number of draws with
+    a weight above 0, and from them ``log_evidence = log_max + log(W1/N)``, its standard error
+    ``log_evidence_stderr = sqrt((N·W2/W1² − 1)/(N − 1))`` (the delta method),
+    ``ess = W1²/W2`` and ``efficiency = ess/N``."""
+
+    def __init__(self, w, stats, n_draws: int, device_w=None):
+        st = np.asarray(stats, dtype=np.float64).reshape(-1, 4)
+        self.w, self.n_draws, self._device_w = w, int(n_draws), device_w
+        self.log_max, self.sum_w, self.sum_w2 = st[:, 0].copy(), st[:, 1].copy(), st[:, 2].copy()
+        with np.errstate(invalid="ignore"):
+            self.n_positive = st[:, 3].astype(np.int64)
+
+    @property
+    def log_evidence(self) -> np.ndarray:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return self.log_max + np.log(self.sum_w / float(self.n_draws))
+
+    @property
+    def ess(self) -> np.ndarray:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return self.sum_w * self.sum_w / self.sum_w2
+
+    @property
+    def efficiency(self) -> np.ndarray:
+        return self.ess / float(self.n_draws)
+
+    @property
+    def log_evidence_stderr(self) -> np.ndarray:
+        N = float(self.n_draws)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            var = (N * self.sum_w2 / (self.sum_w * self.sum_w) - 1.0) / (N - 1.0)
+            return np.sqrt(np.where(var < 0.0, 0.0, var))        # (a rounding below 0 at equal weights)
+
+    def normalized(self):
+        """``w / Σ w`` per point in float64, shape ``(M, N)``: weights that sum to 1."""
+        if isinstance(self.w, np.ndarray):
+            return self.w.astype(np.float64) / self.sum_w[:, None]
+        import torch
+
+        return self.w.double() / torch.from_numpy(self.sum_w).to(self.w.device)[:, None]
+
+    def __repr__(self):
+        return f"ImportanceWeights(points={self.sum_w.shape[0]}, n_draws={self.n_draws})"
+
+
+def importance_weights(log_target, log_proposal=None, device=None) -> ImportanceWeights:
+    """The importance weights of per-point draws, on the device (``df_importance_weights``):
+    ``logw = log_target − log_proposal`` (one Float32 subtraction; ``log_proposal=None``:
+    ``log_target`` holds the log-weights themselves), stabilised per point with its largest
+    non-NaN value, exponentiated and summed in fp64 in a fixed order → :class:`ImportanceWeights`.
+    Both arguments are ``(M, N)`` Float32, numpy arrays or device tensors — the ``log q`` of
+    :func:`posterior_draws` and the unnormalised log-posterior at its draws; ``N`` a multiple of 4.
+    Dtype and shape are checked before the library is touched; the values are not (``−inf`` gives
+    weight 0, a NaN or ``+inf``, or a point of ``−inf`` alone, NaN sums for that point only)."""
+    import torch
+
+    from .hip import run_importance_weights
+
+    M, N = _check_mn(log_target, "log_target")
+    if log_proposal is not None:
+        _check_mn(log_proposal, "log_proposal", (M, N))
+    was_np = not isinstance(log_target, torch.Tensor)
+    dev = torch.device(device) if device is not None else _default_device(log_target, log_proposal)
+    lw = _device_rows(log_target, dev)
+    if log_proposal is not None:
+        lw = lw - _device_rows(log_proposal, dev)
+    w = torch.empty((M, N), dtype=torch.float32, device=dev)
+    stats = torch.empty((M, 4), dtype=torch.float64, device=dev)
+    if M > 0:
+        run_importance_weights(lw, M, N, w, stats)
+    torch.cuda.synchronize(dev)
+    return ImportanceWeights(w.cpu().numpy() if was_np else w, stats.cpu().numpy(), N, w)
+
+
+class WeightedPointStats:
+    """What :func:`weighted_stats` returns, float64 numpy arrays over the M points: ``mean``
+    (d, M), ``cov`` (d, d, M), ``std`` the square root of its diagonal, ``cdf`` (d, M) the weighted
+    posterior CDF ``Σ w·[draw[k] < x[k]] / Σ w`` at the points when they were given (else
+    ``None``), ``ess`` (M,) ``= (Σ w)²/Σ w²``, and ``n_draws``."""
+
+    def __init__(self, mean, cov, cdf, ess, n_draws: int):
+        self.mean, self.cov, self.cdf, self.ess, self.n_draws = mean, cov, cdf, ess, int(n_draws)
+
+    @property
+    def std(self) -> np.ndarray:
+        d = self.mean.shape[0]
+        with np.errstate(invalid="ignore"):
+            return np.sqrt(self.cov[np.arange(d), np.arange(d)])
+
+    def zscore(self, x_true) -> np.ndarray:
+        """``(mean − x_true) / std`` per dimension and point."""
+        x_true = np.asarray(x_true, dtype=np.float64)
+        if x_true.shape != self.mean.shape:
+            raise _lib.DimensionMismatch(f"x_true must have size {self.mean.shape}, got {x_true.shape}")
+        return (self.mean - x_true) / self.std
+
+    def __repr__(self):
+        return f"WeightedPointStats(d={self.mean.shape[0]}, points={self.mean.shape[1]}, n_draws={self.n_draws})"
+
+
+def weighted_moments_from_sums(block, d: int, ddof: int = 1):
+    """``(mean (d, M), cov (d, d, M), ess (M,))`` in float64 from the M blocks of
+    ``df_draw_weighted_stats``' ``sums_out`` — ``W1 = Σ w``, ``W2 = Σ w²``, the shift ``c``,
+    ``S1w = Σ w (v − c)`` and the lower triangle of ``S2w = Σ w (v − c)(v − c)ᵀ``:
+    ``mean = c + δ`` with ``δ = S1w/W1`` and
+    ``cov = (S2w/W1 − δδᵀ) / (1 − W2/W1²)``, the reliability-weights correction, evaluated as
+    ``(S2w − S1w S1wᵀ/W1) / (W1 − W2/W1)`` — with unit weights the very operations of
+    :func:`moments_from_sums`; ``ddof=0`` divides by ``W1`` instead.  ``ess = W1²/W2``."""
+    S = 2 + 2 * d + d * (d + 1) // 2
+    blk = np.asarray(block, dtype=np.float64).reshape(-1, S)
+    w1, w2 = blk[:, 0], blk[:, 1]
+    c, s1 = blk[:, 2:2 + d], blk[:, 2 + d:2 + 2 * d]
+    a, b = np.tril_indices(d)                 # row-major lower triangle: index a(a+1)/2 + b
+    s2 = np.empty((blk.shape[0], d, d))
+    s2[:, a, b] = blk[:, 2 + 2 * d:]
+    s2[:, b, a] = blk[:, 2 + 2 * d:]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        den = (w1 - w2 / w1) if ddof else w1
+        cov = (s2 - s1[:, :, None] * s1[:, None, :] / w1[:, None, None]) / den[:, None, None]
+        mean = c + s1 / w1[:, None]
+        ess = w1 * w1 / w2
+    return mean.T, np.moveaxis(cov, 0, -1), ess
+
+
+def weighted_stats(draws, weights, x=None, ddof: int = 1, device=None) -> WeightedPointStats:
+    """The weighted mean, covariance and CDF value per point of draws under importance weights,
+    reduced on the device (``df_draw_weighted_stats``) → :class:`WeightedPointStats`.  ``draws`` is
+    a numpy ``(M, N, d)`` Float32 array or a device tensor of that shape in C order (the layout of
+    :func:`posterior_draws`); ``N`` a multiple of 4, ``d <= 64``.  ``weights`` is an
+    :class:`ImportanceWeights` or an ``(M, N)`` Float32 array or tensor of finite weights ``>= 0``
+    (not checked).  ``x`` (d, M), when given, are the points of the weighted SBC statistic ``cdf``
+    (a Float32 ``<``: a tie or a NaN counts nothing).  ``ddof`` as for
+    :func:`weighted_moments_from_sums`.  With unit weights the sums are those of
+    :func:`posterior_stats` bit for bit."""
+    import torch
+
+    from .hip import run_draw_weighted_stats
+
+    is_t = isinstance(draws, torch.Tensor)
+    if not is_t:
+        draws = np.asarray(draws)
+    if draws.dtype != (torch.float32 if is_t else np.float32):
+        raise _lib.ArgumentError(f"draws must be Float32 (got {draws.dtype})")
+    if len(draws.shape) != 3:
+        raise _lib.DimensionMismatch(f"draws must have size (M, N, d), got {tuple(draws.shape)}")
+    M, N, d = (int(v) for v in draws.shape)
+    if not 1 <= d <= 64:
+        raise _lib.ArgumentError("d must be in 1 .. 64")
+    if isinstance(weights, ImportanceWeights):
+        wsrc = weights._device_w if weights._device_w is not None else weights.w
+    else:
+        wsrc = weights
+    _check_mn(wsrc, "weights", (M, N))
+    if x is not None:
+        if not isinstance(x, torch.Tensor):
+            x = np.asarray(x)
+        if len(x.shape) < 1 or int(x.shape[0]) != d or int(np.prod(x.shape[1:])) != M:
+            raise _lib.DimensionMismatch(f"x must have size ({d}, {M}), got {tuple(x.shape)}")
+    dev = torch.device(device) if device is not None else _default_device(draws, wsrc)
+    xs = _device_rows(draws, dev)
+    wb = _device_rows(wsrc, dev)
+    xb = as_julia_device(x, d, dev, "x")[0] if x is not None else None
+    S = 2 + 2 * d + d * (d + 1) // 2
+    sums = torch.empty((M, S), dtype=torch.float64, device=dev)
+    wrank = torch.empty((M, d), dtype=torch.float64, device=dev) if x is not None else None
+    if M > 0:
+        run_draw_weighted_stats(xs, wb, xb, d, M, N, wrank, sums)
+    torch.cuda.synchronize(dev)
+    blk = sums.cpu().numpy()
+    mean, cov, ess = weighted_moments_from_sums(blk, d, ddof)
+    cdf = None
+    if x is not None:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            cdf = (wrank.cpu().numpy() / blk[:, :1]).T
+    return WeightedPointStats(mean, cov, cdf, ess, N)
+
+
+def importance_posterior_stats(flow: Flow, theta, log_target, n_draws: int = 1024, x=None, dims=None, rng=None,
+                               seed: Optional[int] = None, offset: int = 0, ddof: int = 1):
+    """Importance-corrected posterior summaries of a conditional flow →
+    ``(WeightedPointStats, ImportanceWeights)``: :func:`posterior_draws` on the device, the
+    caller's ``log_target(draws, theta)`` — the unnormalised log-posterior at the draws, a device
+    tensor ``(M, N, d)`` in and a Float32 device tensor ``(M, N)`` out — then
+    :func:`importance_weights` against the draws' ``log q`` and :func:`weighted_stats` under those
+    weights, with the weighted CDF at the points ``x`` (d, dims...) when given.  Between the draw
+    and the per-point blocks nothing leaves the device; the result is bitwise the composition of
+    the three calls.  ``theta``, ``dims``, ``n_draws`` and the seed arguments as for
+    :func:`posterior_stats`."""
+    dims = _check_point_draws(flow, x, theta, n_draws, 0, dims)
+    draws, lq = posterior_draws(flow, theta, n_draws=n_draws, dims=dims, rng=rng, seed=seed, offset=offset,
+                                as_tensor=True)
+    iw = importance_weights(log_target(draws, theta), lq)
+    return weighted_stats(draws, iw, x, ddof=ddof), iw
 
 
 def pdf(flow: Flow, x, theta=None):

@@ -22,7 +22,7 @@ from . import _lib
 from .layers import (CouplingBlock, NICECouplingLayer, NormalizationLayer, RNVPCouplingLayer)
 
 __all__ = ["HIPChain", "flatten_elements", "as_julia_device", "julia_empty", "chain_dims", "run_order_statistics",
-           "run_draw_histograms"]
+           "run_draw_histograms", "run_importance_weights", "run_draw_weighted_stats"]
 
 
 def _torch():
@@ -233,6 +233,37 @@ def run_draw_histograms(xs, d: int, n_points: int, n_draws: int, edges, bins, ke
         _lib.check(lib.df_draw_histograms(_ptr(xs), C.c_int(d), C.c_int64(n_points), C.c_int64(n_draws), _ptr(edges),
                                           barr, karr, C.c_int32(nt), _ptr(counts), _stream(xs.device)),
                    "draw_histograms")
+
+
+def run_importance_weights(logw, n_points: int, n_draws: int, w=None, stats=None):
+    """df_importance_weights: the float32 device tensor ``logw`` (n_points · n_draws, draw j of
+    point i at ``i·n_draws + j``, 16-byte aligned) into the stabilised weights
+    ``expf(logw − max)`` (float32 device tensor ``w``, not overlapping ``logw``) and, per point, the
+    four float64 ``{max, Σ w, Σ w², #{w > 0}}`` of the device tensor ``stats``; at least one of
+    the two.  On ``logw``'s device and its current stream."""
+    import torch
+
+    lib = _lib.load()
+    with torch.cuda.device(logw.device):
+        _lib.check(lib.df_importance_weights(_ptr(logw), C.c_int64(n_points), C.c_int64(n_draws), _ptr(w),
+                                             _ptr(stats), _stream(logw.device)), "importance_weights")
+
+
+def run_draw_weighted_stats(xs, w, x, d: int, n_points: int, n_draws: int, wrank=None, sums=None):
+    """df_draw_weighted_stats: the ``n_points`` points of the device tensor ``xs`` (d, n_points ·
+    n_draws; draw j of point i at ``d·(i·n_draws + j)``) under the float32 weights ``w`` (n_points ·
+    n_draws), both 16-byte aligned, reduced per point.  ``wrank`` (float64, d · n_points; needs the
+    points ``x`` (d, n_points)) takes ``Σ w·[draw[k] < x[k]]``, ``sums`` (float64, n_points blocks of
+    2 + 2d + d(d+1)/2) ``Σ w``, ``Σ w²``, the shift, ``Σ w·(draw − c)`` and the lower triangle of
+    ``Σ w·(draw − c)(draw − c)ᵀ``; at least one of the two.  On ``xs``' device and its current
+    stream."""
+    import torch
+
+    lib = _lib.load()
+    with torch.cuda.device(xs.device):
+        _lib.check(lib.df_draw_weighted_stats(_ptr(xs), _ptr(w), _ptr(x), C.c_int(d), C.c_int64(n_points),
+                                              C.c_int64(n_draws), _ptr(wrank), _ptr(sums), _stream(xs.device)),
+                   "draw_weighted_stats")
 
 
 class HIPChain:

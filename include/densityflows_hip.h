@@ -469,6 +469,72 @@ int df_flow_point_histograms(df_chain* chain, const float* theta_raw, int64_t n_
                              const int32_t* bins, const int32_t* keep, int32_t n_tables, int32_t* counts_out,
                              float* draws_out, void* stream);
 
+/* ---- importance weights: evidence, ESS, weighted moments per point (additive to ABI 5) ----
+ * What follows df_flow_sample_logpdf: the draws of q(. | θ_i) are weighted with
+ * w = p̃(x) / q(x | θ_i), p̃ the caller's unnormalised target.  Both calls run on the current
+ * device (as df_order_statistics) on the caller's arrays, per point, in fp64, in a fixed order
+ * without atomics: two calls give the same bytes, and so does point i computed alone with the
+ * pointers advanced.  All pointers are DEVICE memory.  Neither call synchronises, zeroes
+ * anything or owns a workspace: both are capturable.  The point mapping follows from n_draws as
+ * in df_flow_point_stats (df_iw.hip states the order of every sum).
+ *
+ * df_importance_weights: per-draw log-weights into stabilised weights and their sums.
+ *   logw (n_points · n_draws) Float32, 16-byte aligned, draw j of point i at i·n_draws + j:
+ *        log p̃ − log q, formed by the caller.
+ *   m_i  the largest non-NaN logw of point i (fmaxf; exact).
+ *   w_out[i·n_draws + j] = expf(logw_ij − m_i): one Float32 subtraction, then the library's
+ *        expf; the largest weight of a point is 1.  Any 4-byte aligned pointer; it must not
+ *        overlap logw (not checked).
+ *   stats_out: 4 doubles per point, { (double)m_i, W1 = Σ_j (double)w_ij, W2 = Σ_j (double)w_ij²,
+ *        n_pos = #{j : w_ij > 0} as a double }.  The squares are exact in fp64: only the
+ *        additions round.
+ * Either output may be NULL, not both.  From the block the host forms
+ *   log Ẑ_i = m_i + log(W1/N),  ESS_i = W1²/W2,  stderr(log Ẑ_i) = sqrt((N·W2/W1² − 1)/(N − 1)).
+ * Nothing is checked on the device (a check would synchronise): logw = −inf gives weight 0; a NaN
+ * logw gives a NaN weight for that draw and NaN W1, W2 for its point only (m_i and n_pos, which
+ * does not count it, stay numbers); a +inf logw makes m_i = +inf, the weight of that draw NaN,
+ * every other weight of the point 0 and W1, W2 NaN; a point whose logw are all −inf has
+ * m_i = −inf, every weight and W1, W2 NaN and n_pos 0.  Other points are not touched.
+ * Checked in this order before any device work, also for an empty call: n_points >= 0
+ * (DF_ERR_SHAPE); n_draws a positive multiple of 4 (DF_ERR_INVALID: the draws come from calls
+ * with that rule, and a point's row stays 16-byte aligned) and at most 2^24
+ * (DF_ERR_UNSUPPORTED); logw non-null and 16-byte aligned (DF_ERR_INVALID); w_out and stats_out
+ * both NULL (DF_ERR_INVALID); n_points · n_draws within int64 (DF_ERR_SHAPE).  Then
+ * n_points == 0: DF_OK, nothing launched, nothing written.
+ *
+ * df_draw_weighted_stats: the weighted sibling of df_flow_point_stats' reduction.
+ *   xs (d, n_points·n_draws) 16-byte aligned, draw j of point i at xs + d·(i·n_draws + j): the
+ *        layout of draws_out.  w (n_points · n_draws) Float32, 16-byte aligned, as w_out above:
+ *        any weights, expected finite and >= 0 (not checked).  x (d, n_points): the points,
+ *        needed with wrank_out only.
+ *   wrank_out[i·d + k] = Σ_j (double)w_ij · [draw_ij[k] < x_i[k]], the Float32 comparison of
+ *        df_flow_point_stats: a tie counts nothing, a NaN on either side counts nothing.
+ *        Divided by W1 it is the weighted posterior CDF at the point: the weighted SBC statistic.
+ *   sums_out: n_points blocks of 2 + 2d + d(d+1)/2 doubles.  Block i:
+ *          W1, W2                              Σ_j w_ij, Σ_j w_ij², in double
+ *          c[k] at 2 + k                       the shift: draw 0 of point i, as a double
+ *          S1w[k] at 2 + d + k                 Σ_j w_ij·(draw_ij[k] − c[k])
+ *          S2w[a, b] at 2 + 2d + a(a+1)/2 + b, a >= b
+ *                                              Σ_j w_ij·(draw_ij[a] − c[a])·(draw_ij[b] − c[b])
+ *        every value converted to double first; w·(v_a − c_a) is one fp64 multiply, and its
+ *        product with (v_b − c_b) (with 1.0 for S1w) is fused into the running sum.  The order
+ *        of these sums is df_flow_point_stats': with every weight 1.0f, entries [2, ..) are that
+ *        call's block of the same draws bit for bit, wrank_out its rank_out and W1 = W2 = n_draws.
+ *        mean = c + S1w/W1, cov = S2w/W1 − δδᵀ with δ = S1w/W1, times 1/(1 − W2/W1²) for the
+ *        reliability-weights correction.  A NaN draw makes the sums it touches NaN (a NaN in
+ *        draw 0 every entry of its dimension), a NaN weight every sum of its point that its row
+ *        enters; nothing is checked.
+ * Either output may be NULL, not both; what is not asked for is not computed.
+ * Checked in this order before any device work, also for an empty call: 1 <= d <= 64
+ * (DF_ERR_INVALID); n_points, then n_draws, as above; xs and w non-null and 16-byte aligned
+ * (DF_ERR_INVALID); both outputs NULL, or wrank_out without x (DF_ERR_INVALID); the sizes within
+ * int64 (DF_ERR_SHAPE).  Then n_points == 0: DF_OK, nothing launched, nothing written. */
+int df_importance_weights(const float* logw, int64_t n_points, int64_t n_draws, float* w_out, double* stats_out,
+                          void* stream);
+
+int df_draw_weighted_stats(const float* xs, const float* w, const float* x, int d, int64_t n_points, int64_t n_draws,
+                           double* wrank_out, double* sums_out, void* stream);
+
 /* ---- grid logpdf------------------------------------------------------------
  * logpdf(flow, (x_1, ..., x_d), (θ_1, ..., θ_n)) (src/Flows.jl:287-331; pdf, :348-349, is
  * its exp): the log-density on the outer product of one vector per dimension, generated on
