@@ -17,6 +17,7 @@ from .flows import (HIST_MAX_BINS, HIST_MAX_TABLES, HIST_SPLIT_DRAWS, QUANT_MAX_
                     ImportanceWeights, MvNormal, PointHistograms, PointStats, Region, ScoreMoments,
                     WeightedPointStats, credible_intervals, importance_posterior_stats, importance_weights,
                     posterior_draws, weighted_moments_from_sums, weighted_stats,
+                    RESAMPLE_LDS_DRAWS, RESAMPLE_METHODS, importance_resample, resample, resample_indices,
                     draw_histograms, entropy, expected_coverage, fisher_information, histogram_edges, hpd_levels,
                     logpdf,
                     logpdf_grad, logpdf_grid, nll_partial_sum, order_statistics, pdf, pdf_marginals,

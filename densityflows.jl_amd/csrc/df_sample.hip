@@ -15,26 +15,10 @@
 
 #include "densityflows_hip.h"
 #include "df_handle.h"
+#include "df_philox.h"
 
 namespace df {
 namespace {
-
-struct U4 {
-    uint32_t x, y, z, w;
-};
-
-__device__ __forceinline__ U4 philox4x32_10(U4 c, uint32_t k0, uint32_t k1) {
-    constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(M0, c.x), lo0 = M0 * c.x;
-        const uint32_t hi1 = __umulhi(M1, c.z), lo1 = M1 * c.z;
-        c = U4{hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
-        k0 += W0;
-        k1 += W1;
-    }
-    return c;
-}
 
 __device__ __forceinline__ float unit_open(uint32_t w) {  // (0, 1), never 0 or 1
     return (float)(w >> 8) * 5.9604644775390625e-08f + 2.98023223876953125e-08f;

@@ -21,7 +21,8 @@ __all__ = ["Flow", "MvNormal", "predict", "sample", "sample_logpdf", "sample_wit
            "posterior_quantiles", "credible_intervals", "HIST_MAX_BINS", "HIST_MAX_TABLES", "HIST_SPLIT_DRAWS",
            "histogram_edges", "draw_histograms", "posterior_histograms", "PointHistograms", "posterior_draws",
            "ImportanceWeights", "importance_weights", "WeightedPointStats", "weighted_moments_from_sums",
-           "weighted_stats", "importance_posterior_stats"]
+           "weighted_stats", "importance_posterior_stats", "RESAMPLE_METHODS", "RESAMPLE_LDS_DRAWS",
+           "resample_indices", "resample", "importance_resample"]
 
 LOG2PI = float(np.log(2.0 * np.pi))
 
@@ -1739,6 +1740,131 @@ def importance_posterior_stats(flow: Flow, theta, log_target, n_draws: int = 102
                                 as_tensor=True)
     iw = importance_weights(log_target(draws, theta), lq)
     return weighted_stats(draws, iw, x, ddof=ddof), iw
+
+
+# ---------------------------------------------------------------------------
+# importance resampling: exact picks and gathered draws (df_resample.hip)
+# ---------------------------------------------------------------------------
+
+RESAMPLE_METHODS = {"systematic": 0, "stratified": 1, "multinomial": 2}
+RESAMPLE_LDS_DRAWS = 4096          # DF_RESAMPLE_LDS_DRAWS: above it the call needs a workspace
+
+
+def _check_resample(weights, n_out, method):
+    """The host checks of a resampling call, no library call → ``(weights array, M, N, K, method
+    code)``."""
+    if not isinstance(method, str) or method not in RESAMPLE_METHODS:
+        raise _lib.ArgumentError(f"unknown resampling method {method!r}: one of {', '.join(RESAMPLE_METHODS)}")
+    if isinstance(weights, ImportanceWeights):
+        wsrc = weights._device_w if weights._device_w is not None else weights.w
+    else:
+        wsrc = weights
+    M, N = _check_mn(wsrc, "weights")
+    K = _check_n_out(n_out, N)
+    return wsrc, M, N, K, RESAMPLE_METHODS[method]
+
+
+def _check_n_out(n_out, N: int) -> int:
+    K = N if n_out is None else int(n_out)
+    if K <= 0 or K % 4 != 0:
+        raise _lib.ArgumentError("n_out must be a positive multiple of 4")
+    if K > MAX_CHUNK:
+        raise _lib.UnsupportedError("a point has at most 2^24 picks (n_out)")
+    return K
+
+
+def _run_resample(xs, wsrc, d, M, N, K, code, seed, offset, want_draws, want_idx, dev):
+    """One ``df_draw_resample`` call on checked arguments → device tensors ``(draws (M, K, d) or
+    None, indices (M, K) or None)``; nothing synchronises."""
+    import torch
+
+    from .hip import run_draw_resample
+
+    wb = _device_rows(wsrc, dev)
+    out = torch.empty((M, K, d), dtype=torch.float32, device=dev) if want_draws else None
+    idx = torch.empty((M, K), dtype=torch.int32, device=dev) if want_idx else None
+    ws = torch.empty((M, N), dtype=torch.int64, device=dev) if N > RESAMPLE_LDS_DRAWS else None
+    if M > 0:
+        run_draw_resample(xs, wb, d, M, N, K, code, seed, int(offset), out, idx, ws)
+    return out, idx
+
+
+def resample_indices(weights, n_out: Optional[int] = None, method: str = "systematic", rng=None,
+                     seed: Optional[int] = None, offset: int = 0, device=None):
+    """Per point ``n_out`` picks among its N weighted draws, on the device (``df_draw_resample``
+    without the gather) → ``(M, n_out)`` int32 indices within the point, numpy for numpy weights and
+    a device tensor otherwise.  ``weights`` is an :class:`ImportanceWeights` or an ``(M, N)`` Float32
+    array or tensor; ``n_out`` (default N) a multiple of 4; ``method`` one of ``"systematic"``,
+    ``"stratified"`` (both non-decreasing in k) and ``"multinomial"`` (stream order).  The picks are
+    exact integer arithmetic on the weights quantised to 32 bits below the point's largest (the
+    header states the contract): bitwise reproducible at a ``(seed, offset)``; a weight that is
+    NaN, ±inf, negative or 0 is never picked, and a point without any other gives −1 throughout.
+    Method, dtype, shape and ``n_out`` are checked before the library is touched."""
+    import torch
+
+    wsrc, M, N, K, code = _check_resample(weights, n_out, method)
+    seed = _draw_seed(rng, seed)
+    was_np = not isinstance(weights.w if isinstance(weights, ImportanceWeights) else weights, torch.Tensor)
+    dev = torch.device(device) if device is not None else _default_device(wsrc)
+    _, idx = _run_resample(None, wsrc, 0, M, N, K, code, seed, offset, False, True, dev)
+    return idx.cpu().numpy() if was_np else idx
+
+
+def resample(draws, weights, n_out: Optional[int] = None, method: str = "systematic", rng=None,
+             seed: Optional[int] = None, offset: int = 0, return_indices: bool = False, device=None):
+    """Weighted draws resampled to equally weighted ones, on the device (``df_draw_resample``) →
+    ``(M, n_out, d)`` Float32: row k of point i is the draw :func:`resample_indices` picks, copied bit
+    for bit (all-NaN where the pick is −1).  ``draws`` is a numpy ``(M, N, d)`` Float32 array or a
+    device tensor of that shape in C order, ``d <= 64``; the result is numpy for numpy draws and
+    stays on the device for a tensor — the layout :func:`order_statistics`, :func:`draw_histograms`
+    and :func:`weighted_stats` (at unit weights) take.  The other arguments as for
+    :func:`resample_indices`; with ``return_indices=True`` the value is ``(draws, indices)``."""
+    import torch
+
+    is_t = isinstance(draws, torch.Tensor)
+    if not is_t:
+        draws = np.asarray(draws)
+    if draws.dtype != (torch.float32 if is_t else np.float32):
+        raise _lib.ArgumentError(f"draws must be Float32 (got {draws.dtype})")
+    if len(draws.shape) != 3:
+        raise _lib.DimensionMismatch(f"draws must have size (M, N, d), got {tuple(draws.shape)}")
+    d = int(draws.shape[2])
+    if not 1 <= d <= 64:
+        raise _lib.ArgumentError("d must be in 1 .. 64")
+    wsrc, M, N, K, code = _check_resample(weights, n_out, method)
+    if (M, N) != tuple(int(v) for v in draws.shape[:2]):
+        raise _lib.DimensionMismatch(f"weights must have size {tuple(draws.shape[:2])}, got {(M, N)}")
+    seed = _draw_seed(rng, seed)
+    dev = torch.device(device) if device is not None else _default_device(draws, wsrc)
+    out, idx = _run_resample(_device_rows(draws, dev), wsrc, d, M, N, K, code, seed, offset, True,
+                             bool(return_indices), dev)
+    if not is_t:
+        out = out.cpu().numpy()
+        idx = idx.cpu().numpy() if return_indices else None
+    return (out, idx) if return_indices else out
+
+
+def importance_resample(flow: Flow, theta, log_target, n_draws: int = 1024, n_out: Optional[int] = None,
+                        method: str = "systematic", dims=None, rng=None, seed: Optional[int] = None, offset: int = 0,
+                        as_tensor: bool = False):
+    """Equally weighted draws of the importance-corrected posterior of a conditional flow →
+    ``(draws (M, n_out, d), ImportanceWeights)``: :func:`posterior_draws` on the device, the caller's
+    ``log_target(draws, theta)`` as for :func:`importance_posterior_stats`, :func:`importance_weights`
+    against the draws' ``log q`` and :func:`resample` under those weights, with nothing leaving the
+    device in between; the result is bitwise the composition of the four calls at the same
+    ``(seed, offset)`` (the resampler's Philox stream is disjoint from the draw's).  ``n_out``
+    defaults to ``n_draws``; numpy unless ``as_tensor``.  ``theta``, ``dims``, ``n_draws`` and the
+    seed arguments as for :func:`posterior_stats`; ``method`` and ``n_out`` as for
+    :func:`resample_indices`, checked before the library is touched."""
+    if not isinstance(method, str) or method not in RESAMPLE_METHODS:
+        raise _lib.ArgumentError(f"unknown resampling method {method!r}: one of {', '.join(RESAMPLE_METHODS)}")
+    dims = _check_point_draws(flow, None, theta, n_draws, 0, dims)
+    _check_n_out(n_out, int(n_draws))
+    seed = _draw_seed(rng, seed)
+    draws, lq = posterior_draws(flow, theta, n_draws=n_draws, dims=dims, seed=seed, offset=offset, as_tensor=True)
+    iw = importance_weights(log_target(draws, theta), lq)
+    out = resample(draws, iw, n_out=n_out, method=method, seed=seed, offset=offset)
+    return (out if as_tensor else out.cpu().numpy()), iw
 
 
 def pdf(flow: Flow, x, theta=None):

@@ -22,7 +22,7 @@ from . import _lib
 from .layers import (CouplingBlock, NICECouplingLayer, NormalizationLayer, RNVPCouplingLayer)
 
 __all__ = ["HIPChain", "flatten_elements", "as_julia_device", "julia_empty", "chain_dims", "run_order_statistics",
-           "run_draw_histograms", "run_importance_weights", "run_draw_weighted_stats"]
+           "run_draw_histograms", "run_importance_weights", "run_draw_weighted_stats", "run_draw_resample"]
 
 
 def _torch():
@@ -264,6 +264,25 @@ def run_draw_weighted_stats(xs, w, x, d: int, n_points: int, n_draws: int, wrank
         _lib.check(lib.df_draw_weighted_stats(_ptr(xs), _ptr(w), _ptr(x), C.c_int(d), C.c_int64(n_points),
                                               C.c_int64(n_draws), _ptr(wrank), _ptr(sums), _stream(xs.device)),
                    "draw_weighted_stats")
+
+
+def run_draw_resample(xs, w, d: int, n_points: int, n_draws: int, n_out: int, method: int, seed: int, offset: int,
+                      xs_out=None, idx_out=None, cdf_ws=None):
+    """df_draw_resample: per point ``n_out`` picks among the ``n_draws`` draws of the float32 device
+    tensor ``w`` (n_points · n_draws, 16-byte aligned) by ``method`` (0 systematic, 1 stratified,
+    2 multinomial) from the Philox stream ``(seed, offset)``: the indices within the point (or −1)
+    into the int32 device tensor ``idx_out`` (n_points · n_out) and the picked rows of ``xs``
+    (d, n_points · n_draws; 16-byte aligned) into ``xs_out`` (d, n_points · n_out), which must not
+    overlap ``xs``; at least one of the two, and without ``xs_out`` neither ``xs`` nor ``d`` is
+    looked at.  ``cdf_ws``: a device tensor of n_points · n_draws 8-byte words, needed above 4096
+    draws.  On ``w``'s device and its current stream."""
+    import torch
+
+    lib = _lib.load()
+    with torch.cuda.device(w.device):
+        _lib.check(lib.df_draw_resample(_ptr(xs), _ptr(w), _ptr(cdf_ws), C.c_int(d), C.c_int64(n_points),
+                                        C.c_int64(n_draws), C.c_int64(n_out), C.c_int(method),
+                                        C.c_uint64(seed), C.c_uint64(offset), _ptr(xs_out), _ptr(idx_out), _stream(w.device)), "draw_resample")
 
 
 class HIPChain:

@@ -535,6 +535,75 @@ int df_importance_weights(const float* logw, int64_t n_points, int64_t n_draws, 
 int df_draw_weighted_stats(const float* xs, const float* w, const float* x, int d, int64_t n_points, int64_t n_draws,
                            double* wrank_out, double* sums_out, void* stream);
 
+/* ---- importance resampling -----------------------------------------------------
+ * df_draw_resample: per point, n_out picks among its n_draws weighted draws and, gathered, the
+ * picked rows — the weighted draws of q(. | θ_i) resampled to equally weighted draws of the
+ * corrected posterior, which df_order_statistics, df_draw_histograms and df_draw_weighted_stats
+ * (at unit weights) take unchanged.  No handle: the call runs on the current device on the
+ * caller's arrays.  All pointers are DEVICE memory.  Nothing is zeroed, nothing synchronises,
+ * there are no atomics: the call is capturable.
+ *   xs (d, n_points·n_draws), draw j of point i at xs + d·(i·n_draws + j), and w (n_points ·
+ *        n_draws) Float32: the layouts of df_draw_weighted_stats; both 16-byte aligned.
+ *   idx_out (n_points · n_out) int32: pick k of point i at i·n_out + k, an index within the
+ *        point, in [0, n_draws), or −1.
+ *   xs_out (d, n_points·n_out): the picked rows, row k of point i at xs_out + d·(i·n_out + k),
+ *        copied bit for bit.  It must not overlap xs (not checked).
+ *   Either output may be NULL, not both.  With xs_out NULL, xs and d are not looked at.
+ *   cdf_ws: a caller-owned workspace of n_points · n_draws uint64 words, 8-byte aligned, needed
+ *        when n_draws > DF_RESAMPLE_LDS_DRAWS and ignored otherwise.  Its content after the
+ *        call is unspecified.
+ * The contract is integer arithmetic throughout: the picks are bitwise reproducible and do not
+ * depend on the kernel mapping, the grid, the other points or the chunking of a call.  For one
+ * point with weights w_0 .. w_{N−1}:
+ *   Quantisation.  A weight takes part when it is finite and > 0.  NaN, ±inf, negative values
+ *        and ±0 get q_j = 0 and are never picked.  With wmax the largest weight that takes part
+ *        and wmax = f·2^e, f in [0.5, 1) (frexp),
+ *          q_j = rint(ldexp((double)w_j, 32 − e)), half to even, as uint64:
+ *        the largest q lies in [2^31, 2^32].  Conversion, a power-of-two scale and rint are
+ *        exact or correctly rounded: no division, no exp.  A weight below 2^−33 of the point's
+ *        scale 2^e becomes 0: at most N·2^−33 of the largest weight's mass is lost.
+ *   Scan.  C_0 = 0, C_{j+1} = C_j + q_j, T = C_N < 2^56.
+ *   Pick k of K = n_out: with a numerator num_k and a denominator D, the one j with
+ *          C_j·D <= num_k·T < C_{j+1}·D        (so q_j > 0),
+ *        the products, below 2^112, compared as 128-bit integers; no division.
+ *          DF_RESAMPLE_SYSTEMATIC   one 32-bit word r_i per point,  num_k = k·2^32 + r_i,  D = K·2^32
+ *          DF_RESAMPLE_STRATIFIED   one 32-bit word r_ik per pick,  num_k = k·2^32 + r_ik, D = K·2^32
+ *          DF_RESAMPLE_MULTINOMIAL  one 64-bit word r_ik per pick,  num_k = r_ik,          D = 2^64
+ *        (multinomial: C_j <= umulhi64(r_ik, T) < C_{j+1}).
+ *   Random words: Philox4x32-10 with key = (seed low, seed high) and counter (c low, c high, 1,
+ *        0); the third counter word 1 keeps the stream disjoint from df_random_normal's
+ *        (ctr, 0, 0, 0) at the same (seed, offset).
+ *          systematic    c = offset + i,                    output word 0
+ *          stratified    c = offset + i·(K/4) + k/4,        output word k % 4
+ *          multinomial   c = offset + i·(K/2) + k/2,        output words 2(k%2) (low), 2(k%2)+1 (high)
+ *        A call consumes n_points, n_points·K/4 and n_points·K/2 counters; a call on the points
+ *        [a, b) — pointers advanced — with offset advanced by a, a·K/4 or a·K/2 reproduces the
+ *        whole call's picks for those points.
+ *   Degenerate point (T = 0: no weight takes part): every pick is −1 and every gathered row is
+ *        all-NaN (0x7fc00000).  Other points keep their bits; an index of −1 is never dereferenced.
+ *   Output order: systematic and stratified picks are non-decreasing in k; multinomial picks come
+ *        in stream order, an exchangeable sample.
+ * For any content of w the search stays inside [0, n_draws) and the stores inside the point's own
+ * output block.  The scan lives in LDS up to n_draws = DF_RESAMPLE_LDS_DRAWS (a wave per point up
+ * to 256 draws, a workgroup per point above) and in cdf_ws past it, where the picks of one point
+ * spread over the device; the picks do not depend on the path.
+ * Checked in this order before any device work, also for an empty call: method in 0 .. 2
+ * (DF_ERR_INVALID); n_points, then n_draws, as in df_importance_weights; n_out a positive multiple
+ * of 4 (DF_ERR_INVALID: the result goes straight into the per-point calls, and the Philox counter
+ * boundaries fall between points) and at most 2^24 (DF_ERR_UNSUPPORTED); w non-null and 16-byte
+ * aligned (DF_ERR_INVALID); both outputs NULL (DF_ERR_INVALID); with xs_out: 1 <= d <= 64, xs
+ * non-null and 16-byte aligned (DF_ERR_INVALID); n_draws > DF_RESAMPLE_LDS_DRAWS with cdf_ws NULL
+ * or not 8-byte aligned (DF_ERR_INVALID); the sizes within int64 (DF_ERR_SHAPE).  Then
+ * n_points == 0: DF_OK, nothing launched, nothing written. */
+#define DF_RESAMPLE_SYSTEMATIC 0
+#define DF_RESAMPLE_STRATIFIED 1
+#define DF_RESAMPLE_MULTINOMIAL 2
+#define DF_RESAMPLE_LDS_DRAWS 4096 /* n_draws up to which a point's scan lives in LDS */
+
+int df_draw_resample(const float* xs, const float* w, void* cdf_ws, int d, int64_t n_points, int64_t n_draws,
+                     int64_t n_out, int method, uint64_t seed, uint64_t offset, float* xs_out, int32_t* idx_out,
+                     void* stream);
+
 /* ---- grid logpdf------------------------------------------------------------
  * logpdf(flow, (x_1, ..., x_d), (θ_1, ..., θ_n)) (src/Flows.jl:287-331; pdf, :348-349, is
  * its exp): the log-density on the outer product of one vector per dimension, generated on
