@@ -95,6 +95,10 @@ struct df_chain {
     int tab_bytes = 0;
     size_t lds = 0;
     int n_trainers = 0;         // live df_train handles bound to this chain
+    // The live trainer whose repack() last wrote the packed blobs (nullptr: they hold
+    // plan.trainables).  Its d_params are the parameters the chain evaluates: a trainer created
+    // now starts from them, and df_train_destroy of the owner copies them into plan.trainables.
+    df_train* params_owner = nullptr;
     // wide-net kernel (plan.wide): its own blob, stages, schedules, descriptors
     DevBuf d_wlayers;
     DevBuf d_wstages;

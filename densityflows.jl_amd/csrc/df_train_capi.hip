@@ -103,6 +103,7 @@ int repack(df_train* t, hipStream_t st) {
                                      : launch_repack(static_cast<float*>(m.blob), dst, src, m.n, params, st);
         if (e != hipSuccess) return hip_err(e, "repack kernel launch");
     }
+    t->c->params_owner = t;  // the chain evaluates this trainer's parameters from here on
     return DF_OK;
 }
 
@@ -282,6 +283,7 @@ struct DestroyTrainer {
 template <typename Body>
 int run_captured(df_train* t, StepGraph& g, hipStream_t st, const char* what, Body&& body) {
     const int flow_now = theta_flow(t);
+    t->c->params_owner = t;  // (a replayed step repacks without passing through repack())
     if (g.cap_gen != t->cap_gen || g.partial_gen != t->c->partial_gen || g.flow != flow_now) drop(g);
     auto where = [&](const char* call) { return std::string(call) + "(" + what + ")"; };
     if (!g.exec) {
@@ -359,11 +361,25 @@ extern "C" {
 
 int df_train_destroy(df_train* t) {
     if (!t) return DF_OK;
-    DeviceGuard gd(t->c->device);
+    df_chain* c = t->c;
+    DeviceGuard gd(c->device);
     free_all(t);
-    t->c->n_trainers--;
+    c->n_trainers--;
+    // The chain keeps evaluating this trainer's parameters: its host copy follows them, so that
+    // the next trainer plans its blobs from them and starts from them.  (One synchronisation:
+    // destroy is not hot.  A trainer another one has repacked over leaves nothing behind.)
+    int rc = DF_OK;
+    if (c->params_owner == t) {
+        c->params_owner = nullptr;
+        const size_t nb = sizeof(float) * (size_t)t->tp.n_params;
+        if (nb > 0 && t->d_params.get() && c->plan.trainables.size() == (size_t)t->tp.n_params) {
+            hipError_t e = hipDeviceSynchronize();
+            if (e == hipSuccess) e = hipMemcpy(c->plan.trainables.data(), t->d_params.get(), nb, hipMemcpyDeviceToHost);
+            if (e != hipSuccess) rc = hip_err(e, "df_train_destroy: reading the parameters back");
+        }
+    }
     delete t;
-    return DF_OK;
+    return rc;
 }
 
 int df_train_create(df_train** out, df_chain* c, const df_adam* opt) {
@@ -462,13 +478,28 @@ int df_train_create_opt(df_train** out, df_chain* c, const df_opt_rule* rules, i
         m.n = ms[i].on ? (int64_t)ms[i].dst->size() : 0;
         m.split = ms[i].split;
     }
+    // The parameters the chain evaluates now: those of the live trainer that last repacked it,
+    // else the host copy (df_chain_create, df_chain_set_weights, or the last owner's at its
+    // df_train_destroy).
+    const df_train* owner = c->params_owner;
     const size_t nb = sizeof(float) * (size_t)tp.n_params;
-    if (nb > 0 && (hipMemcpy(t->d_params.get(), P.trainables.data(), nb, hipMemcpyHostToDevice) != hipSuccess ||
+    if (owner && owner->tp.n_params != tp.n_params)
+        return set_err(DF_ERR_HIP, "internal: the chain's trainers disagree on the parameter count");
+    if (owner && hipDeviceSynchronize() != hipSuccess) return set_err(DF_ERR_HIP, "hipDeviceSynchronize");
+    if (nb > 0 && (hipMemcpy(t->d_params.get(), owner ? owner->d_params.get() : (const void*)P.trainables.data(), nb,
+                             owner ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice) != hipSuccess ||
                    hipMemset(t->d_m.get(), 0, nb) != hipSuccess || hipMemset(t->d_v.get(), 0, nb) != hipSuccess ||
                    hipMemset(t->d_grad.get(), 0, nb) != hipSuccess))
         return set_err(DF_ERR_HIP, "initialising the training state failed");
     // (after every allocation a plain-Adam trainer makes: theirs keep their places)
     if (tp.chain_mode && (rc = setup_chain(t)) != DF_OK) return rc;
+    // The blobs uploaded above were planned from the host copy, which is behind a live owner's
+    // parameters: regather them (every map: tests/test_repack_closure.py shows the regather is
+    // complete).  The chain's own blobs get the bytes they hold already.
+    if (owner) {
+        if ((rc = repack(t, nullptr)) != DF_OK) return rc;
+        if ((e = hipDeviceSynchronize()) != hipSuccess) return hip_err(e, "repack");
+    }
     guard.release();
     *out = t;
     return DF_OK;

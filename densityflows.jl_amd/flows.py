@@ -638,7 +638,8 @@ def logpdf_grad(flow: Flow, x, theta=None, state=None):
         tr, h = state.trainer, state.trainer.chain
     else:
         h = flow.hip()
-        # A new trainer starts from the parameters the chain was planned with: hand the chain
+        # A new trainer starts from the parameters its chain evaluates (df_train_create), and the
+        # model may be newer than the chain (weights loaded or edited in Python): hand the chain
         # the model's current ones first.  The library refuses that while another trainer is
         # bound to the chain (it may hold newer parameters than the model): pass it as `state`.
         try:

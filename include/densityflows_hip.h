@@ -738,7 +738,21 @@ typedef struct df_adam {
     float epsilon;
 } df_adam;
 
-/* Optimisers.setup(Adam(...), flow.model): state m = v = 0, βᵗ = β. */
+/* Optimisers.setup(Adam(...), flow.model): state m = v = 0, βᵗ = β.
+ *
+ * A trainer starts from the parameters its chain evaluates at the moment of creation: those
+ * of df_chain_create / the last df_chain_set_weights, or, once a trainer has updated the
+ * chain (a step, df_train_set_params), that trainer's — whether it is still alive or was
+ * destroyed.  df_train_get_params of the new trainer returns them, its first gradient is
+ * taken at them, and its creation changes no bit of what the chain computes.
+ *
+ * df_train_destroy of the trainer that wrote the chain's weights last copies its parameters
+ * into the chain's host plan (one device synchronisation), so that they outlive it; the
+ * chain goes on evaluating them.  Several trainers may be alive on one chain.  Each one
+ * rewrites the chain's packed weights when it updates, so after either of two trainers has
+ * stepped the two have diverged: the chain evaluates the parameters of the one that updated
+ * last, and the other keeps its own vector, state and private weight copies until its next
+ * update puts them back.  Use one trainer at a time unless that is what you want. */
 int df_train_create(df_train** out, df_chain* chain, const df_adam* opt);
 int df_train_destroy(df_train* t);
 /* Form of the reverse sweep behind df_train_gradient.  Every form

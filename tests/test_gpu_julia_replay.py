@@ -170,6 +170,47 @@ def test_julia_sample_train_sample_sequence(cuda):
         c.finalize()
 
 
+def test_julia_train_rule_change_continues(cuda):
+    """train!(flow, data, setup(Adam(1f-3), …)) then train!(flow, data, setup(Adam(1f-4), …)) on
+    one chain: `_trainer!` sees another key, destroys its trainer and creates a new one, which
+    starts from the parameters the chain evaluates (the shim never calls
+    df_train_set_params).  The new trainer reads back the first one's parameters, and its epoch
+    is bitwise the epoch of a new chain created from those parameters."""
+    J.CALLS.clear()
+    J.__init__()
+    data, chain, flow_py = _datatest_flow(seed=3)
+    c = J.HIPFlowChain(chain)
+    flow = J.Flow(c, flow_py.metadata)
+    c2 = None
+    try:
+        J.train_bang(flow, data, Adam(1e-3), epochs=EPOCHS, batchsize=BS, shuffle=False, verbose=False)
+        p1, t1 = c.params.copy(), c.trainer
+        assert not np.array_equal(p1, trainables(chain))
+        n0 = len(J.CALLS)
+        t2 = J._trainer_bang(c, Adam(1e-4))
+        # (the old trainer's staging is released first; no df_train_set_params anywhere)
+        train_calls = [s for s in J.CALLS[n0:] if s.startswith("df_train_")]
+        assert t2 is not t1 and train_calls[:2] == ["df_train_destroy", "df_train_create"], J.CALLS[n0:]
+        assert "df_train_set_params" not in J.CALLS
+        np.testing.assert_array_equal(J.trainables(t2).view(np.uint32), p1.view(np.uint32))
+        J.train_bang(flow, data, Adam(1e-4), epochs=1, batchsize=BS, shuffle=False, verbose=False)
+        assert c.trainer is t2 and len(flow.train_loss) == EPOCHS + 1
+
+        _, chain2, _ = _datatest_flow(seed=3)
+        load_trainables(chain2, p1)
+        c2 = J.HIPFlowChain(chain2)
+        flow2 = J.Flow(c2, flow_py.metadata)
+        J.train_bang(flow2, data, Adam(1e-4), epochs=1, batchsize=BS, shuffle=False, verbose=False)
+        print("train_loss", flow.train_loss, "fresh chain at the phase-1 parameters", flow2.train_loss)
+        assert flow.train_loss[EPOCHS] == flow2.train_loss[0] and flow.valid_loss[EPOCHS] == flow2.valid_loss[0]
+        assert flow.train_loss[EPOCHS] < flow.train_loss[0]       # it continues, it does not start again
+        np.testing.assert_array_equal(c.params.view(np.uint32), c2.params.view(np.uint32))
+    finally:
+        if c2 is not None:
+            c2.finalize()
+        c.finalize()
+
+
 def test_trainer_theta_input_modes(cuda):
     """df_train_set_theta_input: GIVEN never reads the chain's bounds, RAW requires
     them, AUTO follows them (ABI 3 behaviour); a captured graph step is re-captured

@@ -105,9 +105,10 @@ def serialise(desc, path):
 # the matrix
 # ---------------------------------------------------------------------------
 
-def _bench_configs():
-    """Configurations 2, 1 and 4 as tests/test_host.py builds them, seed 0."""
-    rng = np.random.default_rng(0)
+def _bench_configs(seed=0):
+    """Configurations 2, 1 and 4 as tests/test_host.py builds them, seed 0 (another seed: the
+    same structures with other parameters, tests/test_repack_closure.py)."""
+    rng = np.random.default_rng(seed)
     ch2 = dfa.FlowChain.repeat(dfa.CouplingBlock, 4, 5, hidden_dim_s=64, hidden_dim_t=64, rng=rng)
     x = np.load(os.path.join(HERE, "golden", "datatest_x.npy"))
     th = np.load(os.path.join(HERE, "golden", "datatest_theta.npy"))
@@ -115,7 +116,7 @@ def _bench_configs():
     ch1 = dfa.FlowChain(*[dfa.CouplingLayer(data, m, hidden_dim_s=16, hidden_dim_t=16, rng=rng)
                           for m in ([1, 2, 3], [3, 4, 5], [5, 1, 2])],
                         dfa.NormalizationLayer.from_data(x, -1.0, 1.0))
-    rng = np.random.default_rng(0)
+    rng = np.random.default_rng(seed)
     ch4 = dfa.FlowChain.repeat(dfa.CouplingBlock, 8, 32, n=8, hidden_dim_s=256, hidden_dim_t=256, rng=rng)
     return {"cfg1": describe(ch1.layers), "cfg2": describe(ch2.layers), "cfg4": describe(ch4.layers)}
 
@@ -132,8 +133,8 @@ def _spec_chain(rng, d, n, masks, bias=True, **kw):
 _MASKS = ([1, 2, 3], [4, 5], [5, 1, 2])
 
 
-def _small(**kw):
-    return lambda: _spec_chain(np.random.default_rng(7), 5, 1, _MASKS, **kw)
+def _small(seed=7, **kw):
+    return lambda: _spec_chain(np.random.default_rng(seed), 5, 1, _MASKS, **kw)
 
 
 def _wide_first():
