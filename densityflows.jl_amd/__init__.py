@@ -18,6 +18,9 @@ from .flows import (HIST_MAX_BINS, HIST_MAX_TABLES, HIST_SPLIT_DRAWS, QUANT_MAX_
                     WeightedPointStats, credible_intervals, importance_posterior_stats, importance_weights,
                     posterior_draws, weighted_moments_from_sums, weighted_stats,
                     RESAMPLE_LDS_DRAWS, RESAMPLE_METHODS, importance_resample, resample, resample_indices,
+                    WHIST_MAX_TABLE_BINS, WQUANT_MAX_PROBS, WeightedPointHistograms, importance_credible_intervals,
+                    importance_posterior_histograms, importance_posterior_quantiles, quantile_numerators,
+                    weight_scale, weighted_credible_intervals, weighted_histograms, weighted_quantiles,
                     draw_histograms, entropy, expected_coverage, fisher_information, histogram_edges, hpd_levels,
                     logpdf,
                     logpdf_grad, logpdf_grid, nll_partial_sum, order_statistics, pdf, pdf_marginals,

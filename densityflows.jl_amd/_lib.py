@@ -212,6 +212,11 @@ SIGNATURES = {
     "df_draw_weighted_stats": (C.c_int, [_VP, _VP, _VP, C.c_int, _I64, _I64, _VP, _VP, _VP]),
     "df_draw_resample": (C.c_int, [_VP, _VP, _VP, C.c_int, _I64, _I64, _I64, C.c_int, C.c_uint64, C.c_uint64, _VP,
                                    _VP, _VP]),
+    "df_draw_weight_scale": (C.c_int, [_VP, _I64, _I64, _VP, _VP]),
+    "df_draw_weighted_quantiles": (C.c_int, [_VP, _VP, C.c_int, _I64, _I64, C.POINTER(C.c_uint64), C.c_int, _VP, _VP,
+                                             _VP]),
+    "df_draw_weighted_histograms": (C.c_int, [_VP, _VP, C.c_int, _I64, _I64, _VP, C.POINTER(C.c_int32),
+                                              C.POINTER(C.c_int32), C.c_int32, _VP, _VP, _VP]),
     "df_flow_sample_region": (C.c_int, [_VP, _VP, _VP, _I64, C.POINTER(df_region), _I64, _I64, C.c_uint64,
                                         C.c_uint64, C.POINTER(_I64), C.POINTER(_I64), _VP]),
     "df_flow_logpdf_grid": (C.c_int, [_VP, _VP, C.POINTER(_I64), _I64, _I64, _VP, _I64, _VP]),

@@ -25,8 +25,9 @@ struct Builder {
     const int32_t* bins;
     const std::vector<int32_t>* edge_src;
     int teams;
+    int width = 1;  // 4-byte words of a bin
     HistGroup g = {};
-    int raw_table_words = 0;
+    int raw_table_words = 0;  // the tables' bins
 
     int slot(int dim) const {
         for (int s = 0; s < g.n_dims; ++s)
@@ -46,7 +47,7 @@ struct Builder {
         n.out_off[t] = out_off;
         n.lds_off[t] = next.raw_table_words;
         next.raw_table_words += (int)table_size(bins, a, b);
-        n.table_words = hs_round4(next.raw_table_words);
+        n.table_words = hs_round4(width * next.raw_table_words);
         if ((int64_t)teams * n.table_words > kHsTableWords ||
             hs_lds_words(n.n_dims, n.edge_words, n.table_words, teams) > kHsLdsWords)
             return false;
@@ -99,7 +100,29 @@ int hist_check_tables(int d, const int32_t* bins, const int32_t* keep, int32_t n
     return DF_OK;
 }
 
+int whist_check_tables(int d, const int32_t* bins, const int32_t* keep, int32_t n_tables, int64_t n_points,
+                       int64_t* block_words, std::string* msg) {
+    int64_t T = 0;
+    const int rc = hist_check_tables(d, bins, keep, n_tables, 0, &T, msg);
+    if (rc != DF_OK) return rc;
+    for (int j = 0; j < n_tables; ++j) {
+        const int a = keep[2 * j], b = keep[2 * j + 1];
+        if (table_size(bins, a, b) > DF_WHIST_MAX_TABLE_BINS)
+            return fail(DF_ERR_UNSUPPORTED, msg,
+                        "keep[" + std::to_string(j) + "] = {" + std::to_string(a) + ", " + std::to_string(b) + "}: a table of " +
+                            std::to_string(table_size(bins, a, b)) + " bins is above DF_WHIST_MAX_TABLE_BINS (8192)");
+    }
+    if (n_points > 0 && n_points > (INT64_MAX / 8) / T) return fail(DF_ERR_SHAPE, msg, "T · n_points past int64");
+    if (block_words) *block_words = T;
+    return DF_OK;
+}
+
 bool hist_plan(int d, const int32_t* bins, const int32_t* keep, int32_t n_tables, int teams, HistPlan* plan) {
+    return hist_plan_width(d, bins, keep, n_tables, teams, 1, plan);
+}
+
+bool hist_plan_width(int d, const int32_t* bins, const int32_t* keep, int32_t n_tables, int teams, int width,
+                     HistPlan* plan) {
     plan->groups.clear();
     std::vector<int32_t> edge_src(d, 0), out_off(n_tables, 0);
     int32_t at = 0;
@@ -130,7 +153,7 @@ bool hist_plan(int d, const int32_t* bins, const int32_t* keep, int32_t n_tables
     // lmax x lmax bins over 2g dimensions) fits
     int g = 1;
     for (int c = kHsGroupDims / 2; c > 1; --c) {
-        const int tw = hs_round4(c * c * lmax * lmax);
+        const int tw = hs_round4(width * c * c * lmax * lmax);
         if (c * c <= kHsGroupTables && (int64_t)teams * tw <= kHsTableWords &&
             hs_lds_words(2 * c, 2 * c * (lmax + 1), tw, teams) <= kHsLdsWords) {
             g = c;
@@ -143,10 +166,10 @@ bool hist_plan(int d, const int32_t* bins, const int32_t* keep, int32_t n_tables
         buckets[{rank_of[a] / g, rank_of[b >= 0 ? b : a] / g}].push_back(j);
     }
 
-    Builder cur{bins, &edge_src, teams};
+    Builder cur{bins, &edge_src, teams, width};
     auto close = [&]() {
         if (cur.g.n_tables > 0) plan->groups.push_back(cur.g);
-        cur = Builder{bins, &edge_src, teams};
+        cur = Builder{bins, &edge_src, teams, width};
     };
     for (const auto& kv : buckets) {
         // the whole bucket beside what the group holds, or a group of its own

@@ -28,7 +28,7 @@ constexpr int kHsTableWords = 16384;  // 64 KiB: one 128 x 128 table
 struct HistGroup {
     int32_t n_dims, n_tables;
     int32_t edge_words;                // Σ (L + 1) over the group's dimensions
-    int32_t table_words;               // Σ table sizes, rounded up to a multiple of 4
+    int32_t table_words;               // Σ table sizes · the bin width in words, rounded up to a multiple of 4
     int16_t dim[kHsGroupDims];         // slot s: the dimension,
     int16_t bins[kHsGroupDims];        //         its L,
     int32_t edge_src[kHsGroupDims];    //         its first edge in the caller's edges array,
@@ -36,7 +36,7 @@ struct HistGroup {
     uint8_t ta[kHsGroupTables];        // table t: slot of the lower dimension (runs fastest),
     uint8_t tb[kHsGroupTables];        //          slot of the higher one, kHs1D: a 1-D table
     int32_t out_off[kHsGroupTables];   //          its offset in a point's block (request order)
-    int32_t lds_off[kHsGroupTables];   //          its offset in a team's tables
+    int32_t lds_off[kHsGroupTables];   //          its offset in a team's tables, in bins
 };
 constexpr uint8_t kHs1D = 0xFF;
 
@@ -61,5 +61,14 @@ int hist_check_tables(int d, const int32_t* bins, const int32_t* keep, int32_t n
 // |A| x |B| tables costs |A| + |B| bin searches per draw.  false: a table does not fit a team's
 // share of the LDS (teams = 4 only: every checked table fits a workgroup's).
 bool hist_plan(int d, const int32_t* bins, const int32_t* keep, int32_t n_tables, int teams, HistPlan* plan);
+
+// The weighted tables (df_whist.hip): bins of `width` 4-byte words — 1: hist_plan, 2: uint64 sums of
+// quantised weights, where table_words doubles within the same budgets (lds_off stays in bins).
+// whist_check_tables: hist_check_tables' rules, then every table within DF_WHIST_MAX_TABLE_BINS
+// (DF_ERR_UNSUPPORTED, the message names the request), then T·n_points 8-byte words within int64.
+int whist_check_tables(int d, const int32_t* bins, const int32_t* keep, int32_t n_tables, int64_t n_points,
+                       int64_t* block_words, std::string* msg);
+bool hist_plan_width(int d, const int32_t* bins, const int32_t* keep, int32_t n_tables, int teams, int width,
+                     HistPlan* plan);
 
 }  // namespace df

@@ -31,6 +31,7 @@
 #include "densityflows_hip.h"
 #include "df_handle.h"
 #include "df_philox.h"
+#include "df_wscale.h"
 
 namespace df {
 namespace {
@@ -62,49 +63,8 @@ __device__ __forceinline__ void rs_wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// the bits of a weight that takes part, 0 otherwise (NaN, ±inf, negative, ±0); among weights
-// that take part the bits order as the values do
-__device__ __forceinline__ uint32_t rs_key(float w) {
-    const uint32_t b = __float_as_uint(w);
-    return b - 1u < 0x7f7fffffu ? b : 0u;
-}
-
-__device__ __forceinline__ uint32_t rs_max4(uint32_t m, const uint32_t k[4]) {
-    const uint32_t a = k[0] > k[1] ? k[0] : k[1], b = k[2] > k[3] ? k[2] : k[3];
-    const uint32_t c = a > b ? a : b;
-    return m > c ? m : c;
-}
-
-__device__ __forceinline__ uint32_t rs_wave_max(uint32_t m) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const uint32_t o = (uint32_t)__shfl_xor((int)m, off, 64);
-        m = m > o ? m : o;
-    }
-    return m;
-}
-
-// e with wmax = f·2^e, f in [0.5, 1), from wmax's bits (not 0)
-__device__ __forceinline__ int rs_exponent(uint32_t maxkey) {
-    const int ef = (int)(maxkey >> 23);
-    return ef ? ef - 126 : (32 - __clz((int)maxkey)) - 149;
-}
-
-// rint(w·2^(32 − e)), half to even, of the weight with bits `key` (0: no part)
-__device__ __forceinline__ uint64_t rs_quant(uint32_t key, int e) {
-    if (key == 0u) return 0;
-    const int ef = (int)(key >> 23);
-    const uint32_t m = ef ? (key & 0x7fffffu) | 0x800000u : key;  // w = m·2^ex, m < 2^24
-    const int ex = ef ? ef - 150 : -149;
-    const int s = ex + 32 - e;  // at most 8 for a normal wmax, at most 31 and m·2^s < 2^32 otherwise
-    if (s >= 0) return (uint64_t)m << s;
-    const int r = -s;
-    if (r > 24) return 0;  // m·2^−r < 1/2
-    uint32_t q = m >> r;
-    const uint32_t rem = m & ((1u << r) - 1u), half = 1u << (r - 1);
-    q += (rem > half || (rem == half && (q & 1u))) ? 1u : 0u;
-    return q;
-}
+// rs_key, rs_max4, rs_wave_max, rs_exponent, rs_quant: df_wscale.h (the quantiser the weighted
+// quantiles and tables share)
 
 __device__ __forceinline__ uint64_t rs_shfl_up(uint64_t v, int off) {
     return (uint64_t)__shfl_up((unsigned long long)v, (unsigned)off, 64);

@@ -22,7 +22,10 @@ __all__ = ["Flow", "MvNormal", "predict", "sample", "sample_logpdf", "sample_wit
            "histogram_edges", "draw_histograms", "posterior_histograms", "PointHistograms", "posterior_draws",
            "ImportanceWeights", "importance_weights", "WeightedPointStats", "weighted_moments_from_sums",
            "weighted_stats", "importance_posterior_stats", "RESAMPLE_METHODS", "RESAMPLE_LDS_DRAWS",
-           "resample_indices", "resample", "importance_resample"]
+           "resample_indices", "resample", "importance_resample", "WQUANT_MAX_PROBS", "WHIST_MAX_TABLE_BINS",
+           "quantile_numerators", "weight_scale", "weighted_quantiles", "weighted_credible_intervals",
+           "WeightedPointHistograms", "weighted_histograms", "importance_posterior_quantiles",
+           "importance_credible_intervals", "importance_posterior_histograms"]
 
 LOG2PI = float(np.log(2.0 * np.pi))
 
@@ -1866,6 +1869,266 @@ def importance_resample(flow: Flow, theta, log_target, n_draws: int = 1024, n_ou
     iw = importance_weights(log_target(draws, theta), lq)
     out = resample(draws, iw, n_out=n_out, method=method, seed=seed, offset=offset)
     return (out if as_tensor else out.cpu().numpy()), iw
+
+
+# ---------------------------------------------------------------------------
+# weighted quantiles and histograms: fixed-point weights, exact (df_wquant.hip, df_whist.hip)
+# ---------------------------------------------------------------------------
+
+WQUANT_MAX_PROBS = 32              # DF_WQUANT_MAX_PROBS
+WHIST_MAX_TABLE_BINS = 8192        # DF_WHIST_MAX_TABLE_BINS
+
+
+def quantile_numerators(probs):
+    """The numerators of the weighted-quantile call: ``num = int(rint(float64(p)·2^32))`` over the
+    fixed denominator 2^32, a list of Python ints in ``[0, 2^32]``.  Probabilities outside [0, 1],
+    NaN, none and more than 32 are refused.  No library call."""
+    p = np.atleast_1d(np.asarray(probs, dtype=np.float64)).reshape(-1)
+    if p.size == 0:
+        raise _lib.ArgumentError("no probabilities")
+    if not np.all((p >= 0.0) & (p <= 1.0)):            # a NaN fails both comparisons
+        raise _lib.ArgumentError("probabilities must lie in [0, 1]")
+    if p.size > WQUANT_MAX_PROBS:
+        raise _lib.ArgumentError(f"{p.size} probabilities, at most {WQUANT_MAX_PROBS} in one call")
+    return [int(v) for v in np.rint(p * 4294967296.0)]
+
+
+def _check_weighted_draws(draws, weights):
+    """The host checks the weighted per-point calls share, no library call → ``(weights array, M, N,
+    d, draws are a tensor)``."""
+    import torch
+
+    is_t = isinstance(draws, torch.Tensor)
+    if not is_t:
+        draws = np.asarray(draws)
+    if draws.dtype != (torch.float32 if is_t else np.float32):
+        raise _lib.ArgumentError(f"draws must be Float32 (got {draws.dtype})")
+    if len(draws.shape) != 3:
+        raise _lib.DimensionMismatch(f"draws must have size (M, N, d), got {tuple(draws.shape)}")
+    M, N, d = (int(v) for v in draws.shape)
+    if not 1 <= d <= 64:
+        raise _lib.ArgumentError("d must be in 1 .. 64")
+    wsrc = _weights_source(weights)
+    _check_mn(wsrc, "weights", (M, N))
+    return wsrc, M, N, d, is_t
+
+
+def _weights_source(weights):
+    if isinstance(weights, ImportanceWeights):
+        return weights._device_w if weights._device_w is not None else weights.w
+    return weights
+
+
+def weight_scale(weights, device=None):
+    """The fixed-point scale of every point's weights, on the device (``df_draw_weight_scale``) →
+    ``(e, T)``, int64 numpy vectors of length M: with ``wmax = f·2^e``, ``f`` in [0.5, 1), the
+    largest finite weight ``> 0`` of the point, ``q_j = rint(w_j·2^(32 − e))`` (half to even; 0 for
+    NaN, ±inf, negative and ±0 weights) and ``T = Σ q_j``.  A point without a weight that takes
+    part is empty: ``(0, 0)``.  ``weights`` is an :class:`ImportanceWeights` or an ``(M, N)`` Float32
+    array or tensor, as for :func:`resample`."""
+    import torch
+
+    from .hip import run_draw_weight_scale
+
+    wsrc = _weights_source(weights)
+    M, N = _check_mn(wsrc, "weights")
+    dev = torch.device(device) if device is not None else _default_device(wsrc)
+    wb = _device_rows(wsrc, dev)
+    scale = torch.empty((M, 2), dtype=torch.int64, device=dev)
+    if M > 0:
+        run_draw_weight_scale(wb, M, N, scale)
+    torch.cuda.synchronize(dev)
+    s = scale.cpu().numpy()
+    return s[:, 0].copy(), s[:, 1].copy()
+
+
+def _run_weighted_quantiles(draws, wsrc, M, N, d, nums, dev):
+    """One ``df_draw_weighted_quantiles`` call on checked arguments → device tensors ``(quantiles
+    (M, d, P) float32, scale (M, 2) int64)``; nothing synchronises."""
+    import torch
+
+    from .hip import run_draw_weighted_quantiles
+
+    xs = _device_rows(draws, dev)
+    wb = _device_rows(wsrc, dev)
+    out = torch.empty((M, d, len(nums)), dtype=torch.float32, device=dev)
+    scale = torch.empty((M, 2), dtype=torch.int64, device=dev)
+    if M > 0:
+        run_draw_weighted_quantiles(xs, wb, d, M, N, nums, out, scale)
+    return out, scale
+
+
+def weighted_quantiles(draws, weights, probs=(0.16, 0.5, 0.84), device=None):
+    """The weighted quantiles ``probs`` of every dimension of every point's draws under importance
+    weights, selected on the device (``df_draw_weighted_quantiles``) → float32 ``(M, d, P)``, a numpy
+    array for numpy draws and a device tensor otherwise.  ``draws`` is a numpy ``(M, N, d)`` Float32
+    array or a device tensor of that shape in C order (the layout of :func:`posterior_draws`);
+    ``N`` a multiple of 4, ``d <= 64``.  ``weights`` is an :class:`ImportanceWeights` or an ``(M, N)``
+    Float32 array or tensor.  The rule is the inverted CDF on the quantised weights ``q_j`` of
+    :func:`weight_scale` — numpy's ``method="inverted_cdf"`` with ``weights=q``: with
+    ``τ = max(1, ceil(num·T / 2^32))`` (``num`` of :func:`quantile_numerators`) the draw with the
+    smallest totalOrder key ``k`` such that ``Σ {q_j : key_j <= k} >= τ``, bit for bit — integer
+    arithmetic, no interpolation, no resampling noise.  ``p = 0`` gives the smallest and ``p = 1``
+    the largest draw with a weight that takes part; NaN draws sort to the ends; an empty point
+    gives NaN.  Dtype, shape and probabilities are checked before the library is touched."""
+    import torch
+
+    wsrc, M, N, d, is_t = _check_weighted_draws(draws, weights)
+    nums = quantile_numerators(probs)
+    dev = torch.device(device) if device is not None else _default_device(draws, wsrc)
+    out, _ = _run_weighted_quantiles(draws, wsrc, M, N, d, nums, dev)
+    if is_t:
+        return out
+    torch.cuda.synchronize(dev)
+    return out.cpu().numpy()
+
+
+def _interval_probs(level):
+    level = float(level)
+    if not 0.0 < level < 1.0:                                 # a NaN fails both comparisons
+        raise _lib.ArgumentError("level must lie in (0, 1)")
+    return ((1.0 - level) / 2, 0.5, (1.0 + level) / 2)
+
+
+def weighted_credible_intervals(draws, weights, level: float = 0.68, device=None):
+    """The equal-tailed weighted credible interval of every point and dimension →
+    ``(lower, median, upper)``, each float32 ``(M, d)``: :func:`weighted_quantiles` at
+    ``probs = ((1 − level)/2, 0.5, (1 + level)/2)``; ``0 < level < 1``."""
+    q = weighted_quantiles(draws, weights, _interval_probs(level), device=device)
+    return q[:, :, 0], q[:, :, 1], q[:, :, 2]
+
+
+class WeightedPointHistograms:
+    """What :func:`weighted_histograms` returns: ``tables``, the dict
+    ``{(a,): (M, L_a), (a, b): (M, L_a, L_b)}`` of uint64 numpy arrays — per bin the sum of the
+    quantised weights of its draws — over the M points, ``edges`` (d Float32 vectors, ``None`` for a
+    dimension without bins), the int64 vectors ``e`` and ``T`` of :func:`weight_scale` that give the
+    sums their unit, ``n_draws`` and ``dims``."""
+
+    def __init__(self, tables, edges, e, T, n_draws: int, dims=()):
+        self.tables, self.edges, self.n_draws, self.dims = tables, edges, int(n_draws), tuple(dims)
+        self.e, self.T = np.asarray(e, np.int64), np.asarray(T, np.int64)
+
+    _key = staticmethod(PointHistograms._key)
+
+    def _per_point(self, v, K):
+        return v.reshape((-1,) + (1,) * len(K))
+
+    def sums(self, K) -> np.ndarray:
+        """The uint64 bins of the table."""
+        return self.tables[self._key(K)]
+
+    def mass(self, K) -> np.ndarray:
+        """``sums · 2^(e − 32)`` in float64: the bins in the units of the caller's weights."""
+        K = self._key(K)
+        return np.ldexp(self.tables[K].astype(np.float64), self._per_point((self.e - 32).astype(np.int32), K))
+
+    def inside(self, K) -> np.ndarray:
+        """The quantised weight inside the table's range per point, uint64 (M,): its sum."""
+        c = self.tables[self._key(K)]
+        return c.reshape(c.shape[0], -1).sum(axis=1, dtype=np.uint64)
+
+    def density(self, K) -> np.ndarray:
+        """``sums / (T · bin width)`` (1-D) or ``/ (T · bin area)`` (2-D) in float64: it integrates
+        to the inside fraction ``inside(K) / T``.  A bin with an infinite edge has density 0; an
+        empty point gives NaN."""
+        K = self._key(K)
+        w = np.diff(self.edges[K[0]].astype(np.float64))
+        if len(K) == 2:
+            w = w[:, None] * np.diff(self.edges[K[1]].astype(np.float64))[None, :]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return self.tables[K].astype(np.float64) / (self._per_point(self.T.astype(np.float64), K) * w)
+
+    def pooled(self, K) -> np.ndarray:
+        """``Σ_i sums_i / T_i`` in float64 over the points that are not empty: every point enters
+        with total weight 1."""
+        K = self._key(K)
+        ok = self.T > 0
+        return (self.tables[K][ok].astype(np.float64) / self._per_point(self.T[ok].astype(np.float64), K)).sum(axis=0)
+
+    def __repr__(self):
+        return f"WeightedPointHistograms(tables={len(self.tables)}, dims={self.dims}, n_draws={self.n_draws})"
+
+
+def weighted_histograms(draws, weights, edges, keep=None, device=None) -> WeightedPointHistograms:
+    """The 1-D and 2-D marginal histograms of every point's draws under importance weights, summed
+    on the device (``df_draw_weighted_histograms``) → :class:`WeightedPointHistograms`.  ``draws``,
+    ``edges`` and ``keep`` as for :func:`draw_histograms` (the same bin rule and tables; a table
+    holds at most 8192 bins), ``weights`` as for :func:`weighted_quantiles`.  A bin holds ``Σ q_j``
+    of the draws :func:`draw_histograms` would have counted there, with the quantised weights
+    ``q_j`` of :func:`weight_scale`, as uint64: integer sums, the same bytes whatever the kernel
+    mapping.  With unit weights every table is the count table shifted left by 31."""
+    import torch
+
+    from .hip import run_draw_weighted_histograms
+
+    wsrc, M, N, d, is_t = _check_weighted_draws(draws, weights)
+    ev, bins = histogram_edges(edges, d)
+    reqs = _histogram_requests(keep, bins)
+    for K in reqs:
+        size = int(np.prod([bins[k] for k in K]))
+        if size > WHIST_MAX_TABLE_BINS:
+            raise _lib.UnsupportedError(f"keep {K}: a table of {size} bins is above {WHIST_MAX_TABLE_BINS}")
+    T = sum(int(np.prod([bins[k] for k in K])) for K in reqs)
+    dev = torch.device(device) if device is not None else _default_device(draws, wsrc)
+    xs = _device_rows(draws, dev)
+    wb = _device_rows(wsrc, dev)
+    eb = torch.from_numpy(np.concatenate([v for v in ev if v is not None])).to(dev)
+    out = torch.empty((M, T), dtype=torch.int64, device=dev)
+    scale = torch.empty((M, 2), dtype=torch.int64, device=dev)
+    if M > 0:
+        run_draw_weighted_histograms(xs, wb, d, M, N, eb, bins, reqs, out, scale)
+    torch.cuda.synchronize(dev)
+    s = scale.cpu().numpy()
+    tables = _histogram_tables(out.cpu().numpy().view(np.uint64), M, reqs, bins)
+    return WeightedPointHistograms(tables, ev, s[:, 0].copy(), s[:, 1].copy(), N)
+
+
+def _importance_draws(flow: Flow, theta, log_target, n_draws, dims, rng, seed, offset):
+    """:func:`posterior_draws`, the caller's closure and :func:`importance_weights`, all on the
+    device → ``(draws tensor, ImportanceWeights, dims)``."""
+    dims = _check_point_draws(flow, None, theta, n_draws, 0, dims)
+    draws, lq = posterior_draws(flow, theta, n_draws=n_draws, dims=dims, rng=rng, seed=seed, offset=offset,
+                                as_tensor=True)
+    return draws, importance_weights(log_target(draws, theta), lq), dims
+
+
+def importance_posterior_quantiles(flow: Flow, theta, log_target, probs=(0.16, 0.5, 0.84), n_draws: int = 1024,
+                                   dims=None, rng=None, seed: Optional[int] = None, offset: int = 0):
+    """Importance-corrected posterior quantiles of a conditional flow →
+    ``(quantiles (M, d, P) float32 numpy, ImportanceWeights)``: :func:`posterior_draws` on the
+    device, the caller's ``log_target(draws, theta)`` as for :func:`importance_posterior_stats`,
+    :func:`importance_weights` against the draws' ``log q`` and :func:`weighted_quantiles` under
+    those weights, with nothing leaving the device in between; the result is bitwise the
+    composition of the three calls.  The probabilities are checked before the library is touched;
+    ``theta``, ``dims``, ``n_draws`` and the seed arguments as for :func:`posterior_stats`."""
+    quantile_numerators(probs)
+    draws, iw, _ = _importance_draws(flow, theta, log_target, n_draws, dims, rng, seed, offset)
+    return weighted_quantiles(draws, iw, probs).cpu().numpy(), iw
+
+
+def importance_credible_intervals(flow: Flow, theta, log_target, level: float = 0.68, n_draws: int = 1024, dims=None,
+                                  rng=None, seed: Optional[int] = None, offset: int = 0):
+    """``((lower, median, upper), ImportanceWeights)``, each bound float32 ``(M, d)``:
+    :func:`importance_posterior_quantiles` at ``probs = ((1 − level)/2, 0.5, (1 + level)/2)``."""
+    q, iw = importance_posterior_quantiles(flow, theta, log_target, _interval_probs(level), n_draws, dims, rng, seed,
+                                           offset)
+    return (q[:, :, 0], q[:, :, 1], q[:, :, 2]), iw
+
+
+def importance_posterior_histograms(flow: Flow, theta, log_target, edges=None, keep=None, n_draws: int = 1024,
+                                    dims=None, rng=None, seed: Optional[int] = None, offset: int = 0):
+    """The importance-corrected corner plot of a conditional flow →
+    ``(WeightedPointHistograms, ImportanceWeights)``: the chain of
+    :func:`importance_posterior_quantiles` with :func:`weighted_histograms` at its end; ``edges``
+    and ``keep`` as there, checked before the library is touched."""
+    if edges is None:
+        raise _lib.ArgumentError("importance_posterior_histograms needs edges: one entry per dimension")
+    _histogram_requests(keep, histogram_edges(edges, flow.d)[1])
+    draws, iw, dims = _importance_draws(flow, theta, log_target, n_draws, dims, rng, seed, offset)
+    res = weighted_histograms(draws, iw, edges, keep)
+    res.dims = tuple(dims)
+    return res, iw
 
 
 def pdf(flow: Flow, x, theta=None):

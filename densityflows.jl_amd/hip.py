@@ -22,7 +22,8 @@ from . import _lib
 from .layers import (CouplingBlock, NICECouplingLayer, NormalizationLayer, RNVPCouplingLayer)
 
 __all__ = ["HIPChain", "flatten_elements", "as_julia_device", "julia_empty", "chain_dims", "run_order_statistics",
-           "run_draw_histograms", "run_importance_weights", "run_draw_weighted_stats", "run_draw_resample"]
+           "run_draw_histograms", "run_importance_weights", "run_draw_weighted_stats", "run_draw_resample",
+           "run_draw_weight_scale", "run_draw_weighted_quantiles", "run_draw_weighted_histograms"]
 
 
 def _torch():
@@ -283,6 +284,54 @@ def run_draw_resample(xs, w, d: int, n_points: int, n_draws: int, n_out: int, me
         _lib.check(lib.df_draw_resample(_ptr(xs), _ptr(w), _ptr(cdf_ws), C.c_int(d), C.c_int64(n_points),
                                         C.c_int64(n_draws), C.c_int64(n_out), C.c_int(method),
                                         C.c_uint64(seed), C.c_uint64(offset), _ptr(xs_out), _ptr(idx_out), _stream(w.device)), "draw_resample")
+
+
+def run_draw_weight_scale(w, n_points: int, n_draws: int, scale):
+    """df_draw_weight_scale: per point of the float32 device tensor ``w`` (n_points · n_draws, 16-byte
+    aligned) the two int64 ``{e, T}`` of the device tensor ``scale`` — the exponent of its largest
+    weight that takes part and the sum of its quantised weights, ``{0, 0}`` for an empty point.  On
+    ``w``'s device and its current stream."""
+    import torch
+
+    lib = _lib.load()
+    with torch.cuda.device(w.device):
+        _lib.check(lib.df_draw_weight_scale(_ptr(w), C.c_int64(n_points), C.c_int64(n_draws), _ptr(scale),
+                                            _stream(w.device)), "draw_weight_scale")
+
+
+def run_draw_weighted_quantiles(xs, w, d: int, n_points: int, n_draws: int, nums, out, scale):
+    """df_draw_weighted_quantiles: the weighted quantiles at the numerators ``nums`` (host integers in
+    ``[0, 2^32]`` over the denominator 2^32) of every dimension of the ``n_points`` points of the
+    device tensor ``xs`` (d, n_points · n_draws) under the float32 weights ``w`` (n_points · n_draws),
+    both 16-byte aligned, into the float32 device tensor ``out``, element
+    ``(i·d + k)·len(nums) + q``; ``scale`` (int64, 2 per point) takes ``{e, T}``.  On ``xs``' device
+    and its current stream."""
+    import torch
+
+    vals = [int(v) for v in nums]
+    arr = (C.c_uint64 * max(len(vals), 1))(*vals)
+    lib = _lib.load()
+    with torch.cuda.device(xs.device):
+        _lib.check(lib.df_draw_weighted_quantiles(_ptr(xs), _ptr(w), C.c_int(d), C.c_int64(n_points),
+                                                  C.c_int64(n_draws), arr, C.c_int(len(vals)), _ptr(out), _ptr(scale),
+                                                  _stream(xs.device)), "draw_weighted_quantiles")
+
+
+def run_draw_weighted_histograms(xs, w, d: int, n_points: int, n_draws: int, edges, bins, keep, sums, scale):
+    """df_draw_weighted_histograms: the tables ``keep`` of :func:`run_draw_histograms` (``edges``,
+    ``bins`` as there) with, per bin, the sum of the quantised weights of its draws: ``sums`` is an
+    int64 device tensor whose words hold the uint64 sums, per point a block of the tables in request
+    order; ``w`` the float32 weights (n_points · n_draws, 16-byte aligned); ``scale`` (int64, 2 per
+    point) takes ``{e, T}``.  On ``xs``' device and its current stream."""
+    import torch
+
+    barr, karr, nt = _tables_arrays(bins, keep)
+    lib = _lib.load()
+    with torch.cuda.device(xs.device):
+        _lib.check(lib.df_draw_weighted_histograms(_ptr(xs), _ptr(w), C.c_int(d), C.c_int64(n_points),
+                                                   C.c_int64(n_draws), _ptr(edges), barr, karr, C.c_int32(nt),
+                                                   _ptr(sums), _ptr(scale), _stream(xs.device)),
+                   "draw_weighted_histograms")
 
 
 class HIPChain:

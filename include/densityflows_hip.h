@@ -604,6 +604,72 @@ int df_draw_resample(const float* xs, const float* w, void* cdf_ws, int d, int64
                      int64_t n_out, int method, uint64_t seed, uint64_t offset, float* xs_out, int32_t* idx_out,
                      void* stream);
 
+/* ---- weighted quantiles and histograms -----------------------------------------
+ * df_draw_weight_scale, df_draw_weighted_quantiles, df_draw_weighted_histograms: the median
+ * with its interval and the corner plot of per-point draws under importance weights, without
+ * resampling.  No handle: the calls run on the current device on the caller's arrays.  All
+ * pointers are DEVICE memory except nums, bins and keep (HOST arrays read at call time).
+ *   xs (d, n_points·n_draws) and w (n_points · n_draws) Float32: the layouts of
+ *        df_draw_weighted_stats and df_draw_resample; both 16-byte aligned.
+ *   scale_out (2 int64 per point): {e, T} of point i at 2i, an empty point gives {0, 0}.  It is
+ *        required in all three calls: it gives the sums their unit, and it is the hand-off
+ *        between the scale kernel and the main kernel of the two larger calls (no hidden
+ *        workspace, nothing grows).
+ * Everything below is integer arithmetic after the quantisation, so the results are bitwise
+ * reproducible and depend neither on the kernel mapping nor on the grid, the other points or the
+ * split of a point among workgroups.
+ *   Scale of a point (df_draw_resample's, unchanged).  A weight takes part when its bits lie in
+ *        [1, 0x7f7fffff]: finite and > 0.  With wmax = f·2^e, f in [0.5, 1), the largest such
+ *        weight of the point, q_j = rint(w_j·2^(32 − e)), half to even, formed from the bits.
+ *        NaN, ±inf, negative and ±0 weights give q_j = 0.  q_j < 2^32 and T = Σ q_j < 2^56.  A
+ *        point with T = 0 is empty.  A weight below 2^−33 of the scale 2^e becomes 0: at most
+ *        N·2^−33 of the largest weight's mass is dropped; the rounding is at most half a unit of
+ *        2^−32 of the scale per weight; everything past that is exact.
+ *   Weighted quantile.  The target is a numerator nums[q] in [0, 2^32] over the denominator
+ *        2^32 (a probability p maps to rint((double)p·2^32)).  τ = max(1, ceil(num·T / 2^32)),
+ *        the product, below 2^88, as a 128-bit integer.  Per dimension, with key the IEEE
+ *        totalOrder key of df_order_statistics and C(k) = Σ {q_j : key_j <= k}, the result is
+ *        the draw with the smallest key k such that C(k) >= τ, returned with its own bits: the
+ *        inverted-CDF rule on the quantised weights, no interpolation.  num = 0 gives the
+ *        smallest draw with a weight that takes part, num = 2^32 the largest such draw; the
+ *        result is always a draw with q_j > 0 or one that shares its bits.  NaN draws are not
+ *        skipped: they sort to the ends, as in df_order_statistics.  An empty point gives
+ *        0x7fc00000 in every slot.
+ *        quant_out: element (i·d + k)·n_probs + q, the layout of df_order_statistics' out.
+ *   Weighted histogram.  The bin rule, the edge search and the table requests (edges, bins,
+ *        keep, n_tables) are df_draw_histograms'.  A bin holds Σ q_j over the draws
+ *        df_draw_histograms would have counted there, as uint64: at most T, it cannot overflow.
+ *        The mass in the caller's units is bin·2^(e − 32), the normalised mass bin / T.
+ *        sums_out: per point a block of the tables in request order, the layout of counts_out
+ *        with 8-byte words.  A table holds at most DF_WHIST_MAX_TABLE_BINS bins.  Above
+ *        n_draws = DF_HIST_SPLIT_DRAWS a point's draws are divided among workgroups as in
+ *        df_draw_histograms: the blocks are zeroed on the stream and take 64-bit integer atomic
+ *        adds; below, every bin is written with a plain store.
+ *   Unit weights: q_j = 2^31, e = 1; every weighted table is df_draw_histograms' table shifted
+ *        left by 31, and for n_draws a power of two the quantile at num = (r + 1)·2^32/n_draws
+ *        is order statistic r of df_order_statistics, bit for bit.
+ * Checked in this order before any device work, also for an empty call (df_draw_weight_scale:
+ * the rules that name its arguments): 1 <= d <= 64 (DF_ERR_INVALID); n_points >= 0
+ * (DF_ERR_SHAPE); n_draws a positive multiple of 4 (DF_ERR_INVALID) and at most 2^24
+ * (DF_ERR_UNSUPPORTED); every pointer non-null, then xs and w 16-byte aligned (DF_ERR_INVALID);
+ * 1 <= n_probs <= DF_WQUANT_MAX_PROBS (DF_ERR_UNSUPPORTED) and every nums[q] <= 2^32
+ * (DF_ERR_INVALID, the message names the index); the table rules of df_draw_histograms with
+ * their statuses, then a table above DF_WHIST_MAX_TABLE_BINS (DF_ERR_UNSUPPORTED, the message
+ * names the request); the sizes within int64 (DF_ERR_SHAPE).  Then n_points == 0: DF_OK, nothing
+ * launched, nothing written.  Nothing is checked on the device: for any content of xs, w and
+ * edges the reads stay inside the caller's arrays and the stores inside the point's own blocks. */
+#define DF_WQUANT_MAX_PROBS 32
+#define DF_WHIST_MAX_TABLE_BINS 8192 /* one table: 64 KiB of uint64 in LDS */
+
+int df_draw_weight_scale(const float* w, int64_t n_points, int64_t n_draws, int64_t* scale_out, void* stream);
+
+int df_draw_weighted_quantiles(const float* xs, const float* w, int d, int64_t n_points, int64_t n_draws,
+                               const uint64_t* nums, int n_probs, float* quant_out, int64_t* scale_out, void* stream);
+
+int df_draw_weighted_histograms(const float* xs, const float* w, int d, int64_t n_points, int64_t n_draws,
+                                const float* edges, const int32_t* bins, const int32_t* keep, int32_t n_tables,
+                                uint64_t* sums_out, int64_t* scale_out, void* stream);
+
 /* ---- grid logpdf------------------------------------------------------------
  * logpdf(flow, (x_1, ..., x_d), (θ_1, ..., θ_n)) (src/Flows.jl:287-331; pdf, :348-349, is
  * its exp): the log-density on the outer product of one vector per dimension, generated on
