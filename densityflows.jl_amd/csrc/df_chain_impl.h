@@ -45,12 +45,12 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace impl {
 
-// relu = max(0, x) as ONE v_max_i32 on the bit pattern: non-negative floats order
-// like their integer images, negatives and -0 map to +0, and NaNs with the sign
-// bit clear (every NaN the GPU produces) propagate as in Julia.
-__device__ __forceinline__ float relu(float x) {
-    return __int_as_float(__builtin_elementwise_max(__float_as_int(x), 0));
-}
+// relu = max(0, x) as ONE v_maximum3_f32 (x, 0, 0), the IEEE 754-2019 maximum: negatives
+// and -0 map to +0, a NaN of either sign propagates as Julia's max does.  (It was the integer
+// maximum of the bit pattern, which maps a NaN with the sign bit set to +0; not every NaN
+// the GPU hands on has that bit clear: x - t and -s flip it.  uni::relu_fast, the relu of
+// the specialised, FAST, SPLIT and wide kernels, still is that integer maximum.)
+__device__ __forceinline__ float relu(float x) { return __builtin_elementwise_maximum(x, 0.f); }
 
 // Flux 0.16's Dense evaluates σ = NNlib.fast_act(σ, x): tanh → tanh_fast,
 // sigmoid → sigmoid_fast (Float32 methods, NNlib src/activations.jl).

@@ -21,7 +21,13 @@ using impl::Stager;
 
 // relu(x) = max(0, x) as ONE v_max_i32 on the bit pattern: non-negative floats
 // order like their integer images; negative floats (and -0) map to +0; a NaN
-// with the sign bit clear (the canonical quiet NaN) propagates as in Julia.
+// with the sign bit clear propagates as in Julia.  A NaN with the sign bit set orders
+// below zero and becomes +0, where Julia's max returns NaN — and such NaNs do occur:
+// from an x86 host (0f0/0f0), and on the device from x - t and -s, which flip the sign
+// of the NaN they are handed.  A NaN sample can therefore leave with finite transformed
+// dims (tests/test_gpu_nonfinite.py).  The IEEE maximum (one v_maximum3_f32,
+// impl::relu of the generic kernel) propagates both, but measured +0.3 % cycles per
+// launch on the config-2 SPLIT kernel, outside the parent's run-to-run spread.
 __device__ __forceinline__ float relu_fast(float x) {
     return __int_as_float(__builtin_elementwise_max(__float_as_int(x), 0));
 }
